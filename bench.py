@@ -52,7 +52,17 @@ Metric (BASELINE.json): "SNPs/sec standardized (500k x 1M) + GRM GF/s at 1/2/4/8
                Z.dot(Z.T), snpdata.py:203-206, + the single-threaded K += of snpreader.py:655) on a
                50k-iid slice, extrapolated to configs[3].
 
-Run: python bench.py [--gpus N --steps K --warmup W].  N > 1 either under torch.distributed.run
+A plain run measures `value` alone: it generates the packed matrix, runs W warm-up steps, times K
+steps, and prints the line (metric, value, unit, ms_per_step = the mean wall time of one timed
+step, the configuration, the decode launches' event-timed rate, the device ids).  Every other
+leg above, the side layout / copy / fill figures of the roofline, the weak-scaling passes, the
+selfcheck, the CPU baselines and the parity checks against the oracle run only with --full, which
+prints the same line with those fields added.  --dump-outputs DIR (either mode) writes what the
+last timed step left in the block buffer and the stats buffer -- a seeded row sample of every
+column, a few whole columns, the per-SNP stats; < 64 MB -- as DIR/<name>.npy; the synthetic input
+depends on the arguments only, so two builds can be compared file by file.
+
+Run: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR].  N > 1 either under torch.distributed.run
 (RANK / WORLD_SIZE / LOCAL_RANK from the environment) or as a plain `python bench.py --gpus N`, which
 spawns the N rank processes itself before anything touches the GPU and relays rank 0's line.
 """
@@ -91,6 +101,13 @@ def parse(argv=None):
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=3)
     p.add_argument("--warmup", type=int, default=1)
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline: every other leg (selfcheck, decode_c, e2e, beta, grm, grm_f64, grm5, file), "
+                        "the rooflines and stream ceilings, the CPU baselines and the parity checks against the oracle; "
+                        "without it only the timed steps of `value` run")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed step left in the block buffer and the stats "
+                        "buffer (a fixed, seeded sample, <= 64 MB) as DIR/<name>.npy (rank 0)")
     p.add_argument("--n-iid", type=int, default=500_000)
     p.add_argument("--n-sid", type=int, default=1_000_000)
     p.add_argument("--block", type=int, default=2048)
@@ -535,11 +552,63 @@ def shard(m, rank, world):
 WIDE_MIN_BYTES = 512 << 20  # block buffers of >= 512 MB take the wide column pitch
 
 
-def leg_standardize(N, args, dist, n=None, n_sid=None, std=None, a=0.0, b=0.0, miss=0.01, seed=None):
+DUMP_ROWS_BYTES = 44_000_000  # --dump-outputs: the row sample of every buffer column
+DUMP_COLS_BYTES = 8_000_000  # --dump-outputs: a few whole columns
+
+
+def dump_outputs(N, args, path, out, stats, n, ld, lo, m, B):
+    """--dump-outputs: what the last timed step left in the f32 block buffer and the stats buffer,
+    as .npy files under ``path`` (< 64 MB in all).  The buffer holds the shard's last block in its
+    first columns and, behind a partial last block, the rest of the block before it; every such
+    column is sampled at the same rows (the first and last 64 iids and a seeded choice between),
+    and a few columns are written whole.  The sample depends on the arguments only."""
+    nblk = (m + B - 1) // B
+    if args.steps < 1 or nblk < 1:
+        raise SystemExit("bench.py: --dump-outputs needs at least one timed step over at least one SNP")
+    last = m - (nblk - 1) * B
+    ncols = B if nblk > 1 else last
+    j = np.arange(ncols)
+    snp = np.where(j < last, lo + (nblk - 1) * B + j, lo + (nblk - 2) * B + j)
+    rng = np.random.default_rng(args.seed)
+    nrows = max(1, min(n, DUMP_ROWS_BYTES // (4 * ncols)))
+    if nrows == n:
+        rows = np.arange(n)
+    else:
+        edge = min(64, nrows // 2)
+        mid = rng.choice(np.arange(edge, n - edge), size=nrows - 2 * edge, replace=False)
+        rows = np.concatenate([np.arange(edge), np.sort(mid), np.arange(n - edge, n)])
+    nwhole = max(1, min(ncols, DUMP_COLS_BYTES // (4 * n)))
+    cand = np.concatenate([[0, last - 1], rng.permutation(ncols)])  # both ends of the last block, then seeded
+    whole = np.sort(cand[np.sort(np.unique(cand, return_index=True)[1])][:nwhole])
+    N.call("snpmi_stream_sync")
+    values = np.empty((ncols, len(rows)), dtype=np.float32)
+    columns = np.empty((len(whole), n), dtype=np.float32)
+    col = np.empty(n, dtype=np.float32)
+    for c in range(ncols):
+        N.call("snpmi_memcpy_d2h", N.ptr(col), out.at(c * ld * 4), col.nbytes)
+        values[c] = col[rows]
+        hit = np.nonzero(whole == c)[0]
+        if hit.size:
+            columns[hit[0]] = col
+    st = np.empty((ncols, 2), dtype=np.float32)
+    # the stats buffer is written per block from its start: rows past a partial last block are the block before's
+    N.call("snpmi_memcpy_d2h", N.ptr(st), stats.p, st.nbytes)
+    # a SNP without variation has std = inf (its values are all 0): written as 0, so that the files hold
+    # finite numbers only and the difference of two dumps is a number everywhere
+    st[~np.isfinite(st)] = 0.0
+    os.makedirs(path, exist_ok=True)
+    for name, arr in (("values", values), ("values_iid_index", rows.astype(np.float64)),
+                      ("values_snp_index", snp.astype(np.float64)), ("columns", columns),
+                      ("columns_snp_index", snp[whole].astype(np.float64)), ("stats", st)):
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
+def leg_standardize(N, args, dist, n=None, n_sid=None, std=None, a=0.0, b=0.0, miss=0.01, seed=None, dump=None):
     """Stats + decode of this rank's SNP shard of the n x n_sid packed matrix (resident in HBM) in
     blocks of args.block SNPs into an f32 F-order block buffer; Unit by default, Beta(a, b) with
-    std=N.STD_BETA.  Beside the timed steps (untimed): the same kernel on a tight-column buffer
-    (frac_tight) and the measured copy / fill ceilings."""
+    std=N.STD_BETA.  ``dump``: a directory for dump_outputs (rank 0).  With --full, beside the timed
+    steps (untimed): the weak-scaling passes, the same kernel on the other column layout
+    (frac_tight / frac_spread), the measured copy / fill ceilings and the parity sample."""
     n = args.n_iid if n is None else n
     n_sid = args.n_sid if n_sid is None else n_sid
     std = N.STD_UNIT if std is None else std
@@ -599,6 +668,20 @@ def leg_standardize(N, args, dist, n=None, n_sid=None, std=None, a=0.0, b=0.0, m
     N.call("snpmi_stream_sync")
     dist.barrier()
     wall = dist.max(time.perf_counter() - t0)
+    if dump and dist.rank == 0:
+        dump_outputs(N, args, dump, out, stats, n, ld, lo, m, B)
+    launches = args.steps * nblk
+    dec_mean_ms = dec_ms_total / max(launches, 1)
+    # achieved = bytes of all launches / their summed time (the last block of a shard is partial)
+    bytes_per_step = m * ((n + 3) // 4 + 4 * n)
+    achieved_gbs = bytes_per_step * args.steps / (dec_ms_total * 1e-3) / 1e9 if dec_ms_total else 0.0
+    if not args.full:  # the headline alone: nothing beside the timed steps
+        ev.destroy()
+        for d in (packed, lut, stats, out):
+            d.free()
+        return dict(wall=wall, weak_wall=None, dec_mean_ms=dec_mean_ms, achieved_gbs=achieved_gbs,
+                    full_block_bytes=B * ((n + 3) // 4 + 4 * n), launches=launches, nblk=nblk, pitch=pitch, sample=None,
+                    gpu_cols=None, m=m, out_ld=ld, tight=tight, n=n, n_sid=n_sid, steps=args.steps)
     weak_wall = None
     if dist.world > 1:
         # weak figure: every rank streams the whole n_sid per step (its shard `world` times)
@@ -609,11 +692,6 @@ def leg_standardize(N, args, dist, n=None, n_sid=None, std=None, a=0.0, b=0.0, m
         N.call("snpmi_stream_sync")
         dist.barrier()
         weak_wall = dist.max(time.perf_counter() - t1)
-    launches = args.steps * nblk
-    dec_mean_ms = dec_ms_total / max(launches, 1)
-    # achieved = bytes of all launches / their summed time (the last block of a shard is partial)
-    bytes_per_step = m * ((n + 3) // 4 + 4 * n)
-    achieved_gbs = bytes_per_step * args.steps / (dec_ms_total * 1e-3) / 1e9 if dec_ms_total else 0.0
     # side measurement: the same kernel on the other column layout (full blocks only) -- tight columns
     # (what Bed.read(xp='hbm') writes) when the timed buffer is spread, else the spread pitch
     side_ld = tight if ld != tight else args.spread_ld // 16 * 16
@@ -1514,6 +1592,39 @@ def decode_entry(r, label):
                              "column, launch gaps included"}}
 
 
+def headline(args, dist, r1, value, box):
+    """The result line of a plain run: `value` and what the timed steps themselves measured (the
+    decode launches' HIP-event durations).  --full adds the other legs and checks to it."""
+    n = args.n_iid
+    line = {
+        "metric": METRIC, "value": value, "unit": "SNPs/s", "n_gpus": dist.n_gpus, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": r1["wall"] / args.steps * 1e3, "higher_is_better": True,
+        "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": bool(args.full),
+        "config": {"workload": "decode+Unit standardize of the %d iid x %d SNP matrix (packed BED resident in "
+                               "HBM, SnpGen MAF curve, 1%% missing), SNPs split into %d contiguous shard(s), "
+                               "block %d SNPs, f32 F-order block buffer with a %d-float column pitch"
+                               % (n, args.n_sid, dist.world, args.block, r1["out_ld"]),
+                   "n_iid": n, "n_sid": args.n_sid, "n_sid_per_gpu": r1["m"], "block": args.block,
+                   "block_buffer_ld": r1["out_ld"],
+                   "parallelism": "snp-shard x%d" % dist.world,
+                   "process_group": "rccl" if dist.rccl else ("host rehearsal (SNPMI_DIST_HOST: socket barriers, "
+                                                              "ranks share one GPU, host-staged sums and "
+                                                              "all-gathers)" if dist.world > 1 else "none"),
+                   **({"rccl_init_error": RCCL_FALLBACK["error"],
+                       "process_group_note": "RCCL init failed on every rank: the host group carried this "
+                                             "run's collectives (host-staged, not xGMI)"}
+                      if RCCL_FALLBACK else {})},
+        "roofline": {"bound": "hbm", "achieved": r1["achieved_gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": r1["achieved_gbs"] / HBM_PEAK_GBS, "kernel": "k_decode_f<float> (after k_snp_stats)",
+                     "per_launch_bytes": r1["full_block_bytes"], "mean_launch_ms": r1["dec_mean_ms"]},
+        "dump_outputs": args.dump_outputs,
+        "box": box,
+    }
+    if args.hook or args.decode_variant:  # an A/B run, not the default configuration
+        line["config"]["ab_hooks"] = list(args.hook) + (["decode=%d" % args.decode_variant] if args.decode_variant else [])
+    return line
+
+
 def main(argv=None):
     global WD, RANK
     argv = sys.argv[1:] if argv is None else argv
@@ -1575,15 +1686,22 @@ def main(argv=None):
 def run_legs(N, args, dist):
     box = box_info(N, dist)
     selfcheck = None
-    if args.selfcheck == "on":
+    if args.full and args.selfcheck == "on":
         progress("selfcheck (group size, K-tile all-reduce, all-gather)", limit=min(args.watchdog, 180.0))
         selfcheck = leg_selfcheck(N, args, dist)
         PARTIAL["selfcheck"] = selfcheck
     progress("decode + Unit standardize (value)")
-    r1 = leg_standardize(N, args, dist)
+    r1 = leg_standardize(N, args, dist, dump=args.dump_outputs)
     value = args.n_sid * args.steps / r1["wall"]
     PARTIAL.update(value=value, n_gpus=dist.n_gpus, steps=args.steps, warmup=args.warmup,
                    ms_per_step=r1["wall"] / args.steps * 1e3, selfcheck=selfcheck, box=box)
+    if not args.full:
+        if dist.rank == 0:
+            print(json.dumps(headline(args, dist, r1, value, box)), flush=True)
+            PARTIAL["_printed"] = True
+        progress("final barrier")
+        dist.barrier()
+        return
     grm = grm64 = grm5 = dec_c = e2e = beta = filed = None
     if dist.rank == 0:
         progress("decode_c / e2e")
@@ -1716,24 +1834,8 @@ def run_legs(N, args, dist):
                                   "pass": rel <= 1e-5}
                 beta["cpu_baseline"] = cpub
         n = args.n_iid
-        line = {
-            "metric": METRIC, "value": value, "unit": "SNPs/s", "n_gpus": dist.n_gpus, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": r1["wall"] / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "decode+Unit standardize of the %d iid x %d SNP matrix (packed BED resident in "
-                                   "HBM, SnpGen MAF curve, 1%% missing), SNPs split into %d contiguous shard(s), "
-                                   "block %d SNPs, f32 F-order block buffer with a %d-float column pitch"
-                                   % (n, args.n_sid, dist.world, args.block, r1["out_ld"]),
-                       "n_iid": n, "n_sid": args.n_sid, "n_sid_per_gpu": r1["m"], "block": args.block,
-                       "block_buffer_ld": r1["out_ld"],
-                       "parallelism": "snp-shard x%d" % dist.world,
-                       "process_group": "rccl" if dist.rccl else ("host rehearsal (SNPMI_DIST_HOST: socket barriers, "
-                                                                  "ranks share one GPU, host-staged sums and "
-                                                                  "all-gathers)" if dist.world > 1 else "none"),
-                       **({"rccl_init_error": RCCL_FALLBACK["error"],
-                           "process_group_note": "RCCL init failed on every rank: the host group carried this "
-                                                 "run's collectives (host-staged, not xGMI)"}
-                          if RCCL_FALLBACK else {})},
+        line = headline(args, dist, r1, value, box)
+        line.update({
             "weak": ({"value": args.n_sid * args.steps * dist.world / r1["weak_wall"], "unit": "SNPs/s",
                       "workload": "every rank streams 1M SNPs per step (its shard %d times)" % dist.world}
                      if r1["weak_wall"] else None),
@@ -1752,9 +1854,7 @@ def run_legs(N, args, dist):
                         note="the box this line was measured on: device ids, the hipMemset fill and 1:1 copy ceilings "
                              "measured in this process (decode leg buffers), and the SCLK sampled from sysfs during "
                              "each GRM leg (grm*.sclk_mhz) -- compare runs on different boxes against these"),
-        }
-        if args.hook or args.decode_variant:  # an A/B run, not the default configuration
-            line["config"]["ab_hooks"] = list(args.hook) + (["decode=%d" % args.decode_variant] if args.decode_variant else [])
+        })
         print(json.dumps(line), flush=True)
         PARTIAL["_printed"] = True
     # every rank leaves together (rank 0 ran the CPU baselines and the file leg alone)

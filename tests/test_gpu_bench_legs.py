@@ -111,7 +111,7 @@ def test_bench_with_rccl_communicator_world1(collective):
     import json
     import subprocess
 
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-rccl", "--steps", "1", "--warmup", "0",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--force-rccl", "--steps", "1", "--warmup", "0",
            "--n-iid", "4099", "--n-sid", "6000", "--grm-iid", "5000", "--grm-sid", "12000", "--grm-block", "5000",
            "--grm5-iid", "20000", "--grm5-sid", "4096", "--grm5-block", "2048", "--e2e-sid", "4096", "--e2e-passes", "1",
            "--cpu-seconds", "0.2", "--grm-collective", collective, "--beta-iid", "5001", "--beta-sid", "6000",
@@ -142,6 +142,66 @@ def test_bench_with_rccl_communicator_world1(collective):
     assert "+ RCCL all-gather" in g5["workload"]
 
 
+def test_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` (no --full) runs the headline leg only: one JSON line
+    with value = n_sid / ms_per_step over exactly K timed steps and none of the --full legs.
+    --dump-outputs writes the block buffer and stats of the last timed step (float32/float64 .npy,
+    <= 64 MB): 5000 SNPs in blocks of 2048 leave the partial last block (904 columns) in front of
+    the rest of the block before it; 6001 iids exceed the row sample, so the seeded choice runs.
+    Every dumped value equals the oracle's decode + one-pass Unit of the same packed columns, and a
+    second run (in process) writes identical files."""
+    import json
+    import subprocess
+
+    from oracle import oracle as O
+
+    n, m, B = 6001, 5000, 2048
+    small = ["--n-iid", str(n), "--n-sid", str(m), "--block", str(B), "--steps", "2", "--warmup", "1"]
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dump-outputs", a] + small,
+                         capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, out.stdout
+    d = json.loads(lines[0])
+    assert d["metric"] == bench.METRIC and d["unit"] == "SNPs/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["full"] is False
+    assert d["ms_per_step"] > 0 and abs(d["value"] * d["ms_per_step"] * 1e-3 - m) <= 1e-6 * m
+    moved = {"selfcheck", "weak", "cpu_baseline", "parity", "decode_c", "e2e", "beta", "grm", "grm_f64", "grm5", "file"}
+    assert not moved & set(d), sorted(moved & set(d))
+    legs = [ln.split("] ", 1)[1] for ln in out.stderr.splitlines() if ln.startswith("[bench")]
+    assert legs == ["decode + Unit standardize (value)", "final barrier"], legs
+    got = {f[:-4]: np.load(os.path.join(a, f)) for f in os.listdir(a)}
+    assert set(got) == {"values", "values_iid_index", "values_snp_index", "columns", "columns_snp_index", "stats"}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= 64_000_000
+    last = m - 2 * B
+    snp, rows = got["values_snp_index"].astype(np.int64), got["values_iid_index"].astype(np.int64)
+    assert np.array_equal(snp, np.r_[2 * B:m, B + last:2 * B])
+    assert len(rows) < n and np.all(np.diff(rows) > 0) and rows[0] == 0 and rows[-1] == n - 1
+    # the same packed matrix (bench.synth: the seed and missing rate of the headline leg), through the oracle
+    pitch = N.lib().snpmi_packed_pitch(n)
+    dev = bench.Dev(N, pitch * m)
+    bench.synth(N, dev.p, pitch, n, 0, m, 5, 0.01)
+    packed = np.empty((m, pitch), dtype=np.uint8)
+    N.call("snpmi_memcpy_d2h", N.ptr(packed), dev.p, packed.nbytes)
+    dev.free()
+    body = np.ascontiguousarray(packed[:, :(n + 3) // 4]).reshape(-1)
+    ref, _ = O.decode_standardize(body, n, m, dtype=np.float32)
+    assert np.array_equal(got["values"], ref[np.ix_(rows, snp)].T)
+    whole = got["columns_snp_index"].astype(np.int64)
+    assert {2 * B, m - 1} <= set(whole) <= set(snp) and got["columns"].shape == (len(whole), n)
+    assert np.array_equal(got["columns"], ref[:, whole].T)
+    # stats: the f64 one-pass (mean, std) rounded to f32, within one f32 ulp; a non-finite std is dumped as 0
+    st = O.snp_stats(body, n, m)[snp]
+    assert np.isfinite(got["stats"]).all() and np.isfinite(got["values"]).all()
+    np.testing.assert_allclose(got["stats"], np.where(np.isfinite(st), st, 0.0), rtol=2.0 ** -23)
+    args = bench.parse(small + ["--dump-outputs", b])
+    bench.leg_standardize(N, args, FakeDist(0, 1), dump=b)
+    for k, v in got.items():
+        assert np.array_equal(np.load(os.path.join(b, k + ".npy")), v, equal_nan=True), k
+
+
 def test_decode_leg_wide_block_buffer_same_values():
     """A 32 MB-pitch block buffer (--out-ld 8000000; the default timed layout is tight, the spread
     pitch is the side figure) holds the same values as tight columns: 131072 iids x 2048-SNP blocks
@@ -149,7 +209,7 @@ def test_decode_leg_wide_block_buffer_same_values():
     each run times the other layout on the side."""
     from oracle import oracle as O
 
-    base = ["--n-iid", "131072", "--n-sid", "4096", "--block", "2048", "--steps", "1", "--warmup", "0"]
+    base = ["--full", "--n-iid", "131072", "--n-sid", "4096", "--block", "2048", "--steps", "1", "--warmup", "0"]
     wide = bench.leg_standardize(N, bench.parse(base + ["--out-ld", "8000000"]), FakeDist(0, 1))
     tight = bench.leg_standardize(N, bench.parse(base + ["--out-ld", "0"]), FakeDist(0, 1))
     assert wide["out_ld"] == 8_000_000 and tight["out_ld"] == 131072

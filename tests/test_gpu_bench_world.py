@@ -19,7 +19,7 @@ from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
-SMALL = ["--steps", "1", "--warmup", "0", "--n-iid", "4099", "--n-sid", "6000", "--grm-iid", "5000",
+SMALL = ["--full", "--steps", "1", "--warmup", "0", "--n-iid", "4099", "--n-sid", "6000", "--grm-iid", "5000",
          "--grm-sid", "12000", "--grm-block", "5000", "--grm5-iid", "20000", "--grm5-sid", "2048",
          "--e2e-sid", "4096", "--e2e-passes", "1", "--cpu-seconds", "0.2", "--beta-iid", "5001",
          "--beta-sid", "6000", "--file-iid", "3001", "--file-sid", "5000", "--cpu-grm-iid", "3000",

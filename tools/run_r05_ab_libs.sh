@@ -6,8 +6,8 @@ out=gpurun_out/$1
 shift
 mkdir -p $out
 export TMPDIR=/tmp
-GRM="--n-iid 16384 --n-sid 16384 --steps 1 --warmup 0 --skip-cpu --grm-sid 125000 --grm-f64 off --grm5 off --e2e off --beta off --file off"
-T="--n-iid 16384 --n-sid 16384 --steps 1 --warmup 0 --skip-cpu --grm-f64 off --grm5 off --e2e off --beta off --file off"
+GRM="--full --n-iid 16384 --n-sid 16384 --steps 1 --warmup 0 --skip-cpu --grm-sid 125000 --grm-f64 off --grm5 off --e2e off --beta off --file off"
+T="--full --n-iid 16384 --n-sid 16384 --steps 1 --warmup 0 --skip-cpu --grm-f64 off --grm5 off --e2e off --beta off --file off"
 run() {  # name lib hooks cmd...
   local name=$1 lib=$2 hooks=$3; shift 3
   local h=""

@@ -12,7 +12,7 @@ if [ "$WHAT" = tests ]; then
   timeout -k 10 1000 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $OUT/pytest_gpu.log 2>&1
   timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.txt 2>&1
 else
-  timeout -k 10 400 python -u bench.py > $OUT/bench_default.json 2> $OUT/bench.err
+  timeout -k 10 400 python -u bench.py --full > $OUT/bench_default.json 2> $OUT/bench.err
   bash tools/profile_r05.sh $TAG
 fi
 echo validate-done

@@ -12,6 +12,6 @@ if [ "$WHAT" = tests ] || [ "$WHAT" = all ]; then
   timeout -k 10 120 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.txt 2>&1
 fi
 if [ "$WHAT" = bench ] || [ "$WHAT" = all ]; then
-  timeout -k 10 400 python -u bench.py > $OUT/bench_default.json 2> $OUT/bench.err
+  timeout -k 10 400 python -u bench.py --full > $OUT/bench_default.json 2> $OUT/bench.err
 fi
 echo validate-done
