@@ -633,14 +633,49 @@ static void subset_impl(const S* val, uint64_t rows, uint64_t cols, uint64_t k, 
 }
 
 // ====================================================================== GRM
-// f32 GRM of a packed SNP block, N >= 4096: two phases per sub-block of SNPs -- k_decode_f
-// writes the standardized block Z (f32, F order, ld = round_up(N, 256)) to HBM (0.4 ms per
-// 10k SNPs at N=50k), then the dense SYRK streams Z into LDS with global_load_lds and runs
-// MFMA-only (no VALU in its loader): 136.7 TFLOP/s vs 130.9 for the fused LUT-expanding
-// kernel (tools/ubench.py syrk / syrk_dense, N=50k, 10k SNPs).  Sub-blocks keep Z <= 16 GiB.
+// Hook "syrk" (accepted: 0, 5, 20, 36, 71) and the public switch "f64"
+// (pysnptools_amd.set_grm_f64: 1 = every f64 GRM on the f64 MFMA).  The two functions below are
+// the only readers; every launcher asks them for the named path (snpmi_internal.hpp F32Path /
+// F64Path say what each one runs).
+static int g_variant_syrk = 0;
+static int g_f64_mfma = 0;
+static int g_variant_syrk_split = 0;  // tuning hook: 0 = auto, 1 = off, S = force S slices
+static int g_dense_codes = 1;         // tuning / test hook: 0 = dense operands never re-encoded
+
+F32Path syrk_f32_path() {
+    switch (g_variant_syrk) {
+        case 0: return F32Path::H2;
+        case 36: return F32Path::BF3;
+        case 5: return F32Path::TILE128;
+        default: return F32Path::TWO_PHASE;  // 20, 71
+    }
+}
+F64Path syrk_f64_path() {
+    switch (g_variant_syrk) {
+        case 0: return g_f64_mfma ? F64Path::TWO_PHASE : F64Path::CRT;
+        case 5:
+        case 36: return F64Path::FUSED;
+        default: return F64Path::TWO_PHASE;  // 20, 71
+    }
+}
+
+static GrmDest whole_dest(void* tiles, uint64_t n) {
+    const uint64_t nb = ceil_div(n, 256);
+    return {tiles, nullptr, nullptr, nb * (nb + 1) / 2};
+}
+static GrmDest part_dest(void* blocks, uint64_t n, int rank, int world) {
+    const PartTables pt = part_tables(ceil_div(n, 256), rank, world);  // tab != nullptr even for an empty part
+    return {blocks, pt.tab, pt.dslot, grm_part_blocks(n, rank, world)};
+}
+
+// The f32 / f64 MFMA path at N >= 4096 / 1024: two phases per sub-block of SNPs -- k_decode_f
+// writes the standardized block Z (F order, ld = round_up(N, 256)) to HBM (0.4 ms per 10k SNPs at
+// N=50k), then the dense SYRK streams Z into LDS with global_load_lds and runs MFMA-only (no VALU
+// in its loader): 136.7 TFLOP/s vs 130.9 for the fused LUT-expanding f32 kernel (tools/ubench.py
+// syrk / syrk_dense, N=50k, 10k SNPs).  Sub-blocks keep Z <= 16 GiB.
 static bool use_two_phase(int dt, uint64_t n) {
-    if (g_variant_syrk != 0 && g_variant_syrk != 20 && g_variant_syrk != 71) return false;
-    return dt == SNPMI_DT_F32 ? n >= 4096 : n >= 1024;
+    return dt == SNPMI_DT_F32 ? syrk_f32_path() == F32Path::TWO_PHASE && n >= 4096
+                              : syrk_f64_path() == F64Path::TWO_PHASE && n >= 1024;
 }
 
 template <typename T, class F>
@@ -659,28 +694,12 @@ static void for_z_blocks(Device& d, const uint8_t* packed, uint64_t pitch, uint6
     }
 }
 
-// f32 GRM of packed SNPs: default = the bf16 MFMA pipe (k_syrk_bf3: bf16x3 split of each SNP's
-// f32 LUT, six bf16 products per f32 product, f32 accumulate): 309 TFLOP/s at N=50k, 10k SNPs
-// vs 136 for the f32-MFMA two-phase path (variant 20) -- tools/ubench.py syrk.
-// Variants: 30 = plain loader, 31 = + XCD remap, 33 = end-of-stage barrier, 34 = mid-stage
-// barrier without the pinned VALU interleave, 35 = default kernel without split-K, 39 =
-// ablation (no loader); 4/5/20 = f32 MFMA.
-static int g_variant_syrk_split = 0;  // tuning hook: 0 = auto, 1 = off, S = force S slices
-static int g_dense_codes = 1;         // tuning / test hook: 0 = dense operands never re-encoded
-
-static bool use_bf3(int dt) {
-    return dt == SNPMI_DT_F32 && (g_variant_syrk == 0 || (g_variant_syrk >= 30 && g_variant_syrk <= 69));
-}
-// default: the fp16x2 kernel (k_syrk_h2, 3 products) with the bf16x3 kernel as its range
-// fallback; 30-39 force bf16x3 alone
-static bool use_h2() { return g_variant_syrk == 0 || (g_variant_syrk >= 40 && g_variant_syrk <= 69); }
-
-// split-K slices for the bf16x3 SYRK when the 256x256-block grid leaves CUs idle in its last
+// split-K slices for the default f32 chain when the 256x256-block grid leaves CUs idle in its last
 // round: minimise rounds-per-slice ceil(g*S / CUs) / S, +1% per extra slice (partial sets + the
 // reduce), >= 1024 SNPs per slice.  Measured (tools/ubench.py syrk, m = 20k): N=10k 213 -> 242
 // TFLOP/s at S=4, N=5k 199 -> 217 at S=6 -- the slice counts this model picks.
 static int bf3_split_slices(uint64_t n, uint64_t m, int cus) {
-    if (g_variant_syrk == 35 || g_variant_syrk == 45 || g_variant_syrk_split == 1) return 1;
+    if (g_variant_syrk_split == 1) return 1;
     if (g_variant_syrk_split > 1) return g_variant_syrk_split;
     const uint64_t nb = ceil_div(n, 256), g = nb * (nb + 1) / 2, C = (uint64_t)std::max(cus, 1);
     const double unsplit = (double)ceil_div(g, C);
@@ -712,14 +731,6 @@ static const uint32_t* lut_bf3(Device& d, const float* lut, uint64_t m, H2Lut* h
     return l3;
 }
 
-// f64 GRM of packed SNPs: default = the int8 MFMA residue path (syrk_crt.hip; variant 70 forces
-// it), 71 = the f64 MFMA two-phase path (decode to a dense f64 block, then k_syrk_glds).
-static int g_f64_mfma = 0;  // public switch "f64" (pysnptools_amd.set_grm_f64): 1 = every f64 GRM on the f64 MFMA
-static bool use_crt(int dt) {
-    return dt == SNPMI_DT_F64 && !g_f64_mfma &&
-           (g_variant_syrk == 0 || (g_variant_syrk >= 70 && g_variant_syrk != 71 && g_variant_syrk <= 99));
-}
-
 // f32 segment scratch pool of the current device (syrk.hip SegFlush): kSegSlots slots of 256 KiB
 // + their flags, zeroed once when the pool is first allocated (slots are released by the kernels)
 SegCtx seg_ctx() {
@@ -749,11 +760,13 @@ static unsigned long long* crt_record(Device& d) {
     return rec;
 }
 
+// f64 GRM on the int8 MFMA residue path (syrk_crt.hip), crt_max_snps() SNPs per step; a step whose
+// LUT holds NaN/Inf is computed by the f64 MFMA kernel instead (gated on the device flag).  A
+// part's residue chunks follow its layout table and K is written as its dense f64 blocks.
 static void syrk_packed_crt(Device& d, const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m,
-                            const double* lut, double* tiles, int accumulate) {
-    const uint64_t nb = ceil_div(n, 256), blocks = nb * (nb + 1) / 2;
+                            const double* lut, const GrmDest& o, int accumulate) {
     // residue scratch: one byte per modulus and element of the 256-blocks, at most 4 GiB (then chunked)
-    const uint64_t res_bytes = std::min<uint64_t>(blocks * (uint64_t)crt_moduli() * 65536, 4ull << 30);
+    const uint64_t res_bytes = std::min<uint64_t>(o.blocks * (uint64_t)crt_moduli() * 65536, 4ull << 30);
     uint8_t* res = (uint8_t*)d.get(Device::S_ZBLK, res_bytes);
     const uint64_t step = crt_max_snps();
     void* ws = d.get(Device::S_LUT3, crt_lut_bytes(std::min(m, step), n));
@@ -761,130 +774,85 @@ static void syrk_packed_crt(Device& d, const uint8_t* packed, uint64_t pitch, ui
     for (uint64_t s0 = 0; s0 < m; s0 += step) {
         const uint64_t cnt = std::min(step, m - s0);
         const int acc = accumulate || s0 > 0;
-        launch_syrk_packed_crt(packed + s0 * pitch, pitch, n, cnt, lut + 4 * s0, tiles, acc, ws, res, res_bytes,
-                               rec, d.stream);
-        // NaN/Inf in this chunk's LUT: the f64 MFMA kernel computes it (gated on the device flag)
-        launch_syrk_packed_f64_gated(packed + s0 * pitch, pitch, n, cnt, lut + 4 * s0, tiles, acc,
-                                     (const int*)ws + 1, d.stream);
+        launch_syrk_packed_crt(packed + s0 * pitch, pitch, n, cnt, lut + 4 * s0, (double*)o.k, acc, ws, res, res_bytes,
+                               rec, d.stream, nullptr, nullptr, o.tab, o.blocks);
+        launch_syrk_packed(packed + s0 * pitch, pitch, n, cnt, lut + 4 * s0, SNPMI_DT_F64, o, acc, d.stream,
+                           (const int*)ws + 1);
     }
 }
 
-static void syrk_packed_f32_body(Device& d, const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m,
-                                 const void* lut, int dt, void* tiles, int accumulate);
-
-static void syrk_packed_auto(Device& d, const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m,
-                             const void* lut, int dt, void* tiles, int accumulate) {
-    if (use_crt(dt) && m > 0 && n > 0) {
-        syrk_packed_crt(d, packed, pitch, n, m, (const double*)lut, (double*)tiles, accumulate);
-        return;
-    }
-    if (dt == SNPMI_DT_F32 && g_diag_exact && m > 0 && n > 0) {  // exact diagonal around the SYRK
-        double* diag = (double*)d.get(Device::S_DIAG, diag_scratch_bytes(n, m));
-        launch_diag_begin((const float*)tiles, n, nullptr, accumulate, diag, d.stream);
-        syrk_packed_f32_body(d, packed, pitch, n, m, lut, dt, tiles, accumulate);
-        launch_diag_end(packed, pitch, n, m, (const float*)lut, (float*)tiles, nullptr, diag, d.stream);
-        return;
-    }
-    syrk_packed_f32_body(d, packed, pitch, n, m, lut, dt, tiles, accumulate);
-}
-
-static void syrk_packed_f32_body(Device& d, const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m,
-                                 const void* lut, int dt, void* tiles, int accumulate) {
-    if (use_bf3(dt)) {
+// The MFMA paths of both dtypes (everything but the CRT path).  f32 default: the fp16x2 / bf16x3
+// chain (309 TFLOP/s for bf16x3 alone at N=50k, 10k SNPs vs 136 for the f32-MFMA two-phase path --
+// tools/ubench.py syrk); otherwise the two-phase path or the fused kernels.  Two things differ by
+// destination: a part's grid is never split along K, and it has its own dense launcher.
+static void syrk_packed_mfma(Device& d, const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m,
+                             const void* lut, int dt, const GrmDest& o, int accumulate) {
+    const F32Path p32 = syrk_f32_path();
+    if (dt == SNPMI_DT_F32 && (p32 == F32Path::H2 || p32 == F32Path::BF3)) {
         H2Lut h2;
-        const bool h = use_h2() && m > 0;
+        const bool h = p32 == F32Path::H2 && m > 0;
         const uint32_t* l3 = lut_bf3(d, (const float*)lut, m, h ? &h2 : nullptr);
-        const int S = bf3_split_slices(n, m, d.cu_count);
+        const int S = o.tab ? 1 : bf3_split_slices(n, m, d.cu_count);
         if (S > 1) {
             float* part = (float*)d.get(Device::S_ZBLK, (uint64_t)S * n_tiles_upper(n) * kTile * kTile * sizeof(float));
-            launch_syrk_packed_bf3_split(packed, pitch, n, m, l3, S, part, (float*)tiles, accumulate, d.stream,
+            launch_syrk_packed_bf3_split(packed, pitch, n, m, l3, S, part, (float*)o.k, accumulate, d.stream,
                                          h ? &h2 : nullptr);
         } else {
-            launch_syrk_packed_bf3(packed, pitch, n, m, l3, (float*)tiles, accumulate, d.stream, h ? &h2 : nullptr);
+            launch_syrk_packed_bf3(packed, pitch, n, m, l3, o, accumulate, d.stream, h ? &h2 : nullptr);
         }
         return;
     }
     if (!use_two_phase(dt, n) || m == 0) {
-        launch_syrk_packed(packed, pitch, n, m, lut, dt, tiles, accumulate, d.stream);
+        launch_syrk_packed(packed, pitch, n, m, lut, dt, o, accumulate, d.stream);
         return;
     }
     auto run = [&](const void* Z, uint64_t ldz, uint64_t cnt, bool more) {
-        launch_syrk_dense(Z, ldz, n, cnt, dt, tiles, accumulate || more, d.stream);
+        if (o.tab) launch_syrk_dense_part((const float*)Z, ldz, n, cnt, o, accumulate || more, d.stream);
+        else launch_syrk_dense(Z, ldz, n, cnt, dt, o.k, accumulate || more, d.stream);
     };
     if (dt == SNPMI_DT_F32) for_z_blocks(d, packed, pitch, n, m, (const float*)lut, run);
     else for_z_blocks(d, packed, pitch, n, m, (const double*)lut, run);
 }
 
-static void syrk_packed_part_body(Device& d, const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m,
-                                  const float* lut, int rank, int world, void* blocks, int accumulate);
-
-static void syrk_packed_part_auto(Device& d, const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m,
-                                  const float* lut, int rank, int world, void* blocks, int accumulate) {
-    if (g_diag_exact && m > 0 && n > 0) {  // exact diagonal of the part's diagonal blocks
-        double* diag = (double*)d.get(Device::S_DIAG, diag_scratch_bytes(n, m));
-        const int32_t* dslot = part_tables(ceil_div(n, 256), rank, world).dslot;
-        launch_diag_begin((const float*)blocks, n, dslot, accumulate, diag, d.stream);
-        syrk_packed_part_body(d, packed, pitch, n, m, lut, rank, world, blocks, accumulate);
-        launch_diag_end(packed, pitch, n, m, lut, (float*)blocks, dslot, diag, d.stream);
+// K (+)= Z Z^T of a packed SNP block into the whole K or one part: the CRT path for f64, else the
+// MFMA paths, for f32 inside the exact diagonal (hook "diag")
+static void syrk_packed_auto(Device& d, const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m,
+                             const void* lut, int dt, const GrmDest& o, int accumulate) {
+    if (dt == SNPMI_DT_F64 && syrk_f64_path() == F64Path::CRT && m > 0 && n > 0) {
+        syrk_packed_crt(d, packed, pitch, n, m, (const double*)lut, o, accumulate);
         return;
     }
-    syrk_packed_part_body(d, packed, pitch, n, m, lut, rank, world, blocks, accumulate);
+    if (dt == SNPMI_DT_F32 && g_diag_exact && m > 0 && n > 0) {
+        double* diag = (double*)d.get(Device::S_DIAG, diag_scratch_bytes(n, m));
+        launch_diag_begin((const float*)o.k, n, o.dslot, accumulate, diag, d.stream);
+        syrk_packed_mfma(d, packed, pitch, n, m, lut, dt, o, accumulate);
+        launch_diag_end(packed, pitch, n, m, (const float*)lut, (float*)o.k, o.dslot, diag, d.stream);
+        return;
+    }
+    syrk_packed_mfma(d, packed, pitch, n, m, lut, dt, o, accumulate);
 }
 
-// f64 part (cfg5 in the reference's default dtype): the int8 CRT path over the part's layout
-// (launch_syrk_packed_crt with the layout table: residue chunks of the part's blocks, K written as
-// dense f64 blocks), its f64-MFMA fallback gated on the non-finite flag; hook "f64" = 1: every
-// block on the f64 MFMA
+// f64 part (cfg5 in the reference's default dtype): the CRT path over the part's layout; off that
+// path (hooks "syrk" / "f64"), every block on the fused f64 MFMA kernel in the same SNP steps
 static void syrk_packed_part_f64(Device& d, const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m,
                                  const double* lut, int rank, int world, double* blocks, int accumulate) {
-    const uint64_t nloc = grm_part_blocks(n, rank, world);
-    if (nloc == 0) return;
-    SNPMI_REQUIRE(4 * nloc < (1ull << 31), SNPMI_E_ARG, "too many GRM blocks for one launch");
+    const GrmDest o = part_dest(blocks, n, rank, world);
+    if (o.blocks == 0) return;
+    SNPMI_REQUIRE(4 * o.blocks < (1ull << 31), SNPMI_E_ARG, "too many GRM blocks for one launch");
     SNPMI_REQUIRE(pitch % 64 == 0 && pitch * 4 >= ceil_div(n, 256) * 256, SNPMI_E_ARG,
                   "packed pitch must cover round_up(n, 256) iids");
     if (m == 0) {
-        if (!accumulate) SNPMI_HIP(hipMemsetAsync(blocks, 0, nloc * 256 * 256 * sizeof(double), d.stream));
+        if (!accumulate) SNPMI_HIP(hipMemsetAsync(blocks, 0, o.blocks * 256 * 256 * sizeof(double), d.stream));
         return;
     }
-    const PartTables pt = part_tables(ceil_div(n, 256), rank, world);
+    if (syrk_f64_path() == F64Path::CRT) {
+        syrk_packed_crt(d, packed, pitch, n, m, lut, o, accumulate);
+        return;
+    }
     const uint64_t step = crt_max_snps();
-    if (!use_crt(SNPMI_DT_F64)) {
-        for (uint64_t s0 = 0; s0 < m; s0 += step)
-            launch_syrk_packed_f64_gated(packed + s0 * pitch, pitch, n, std::min(step, m - s0), lut + 4 * s0, blocks,
-                                         accumulate || s0 > 0, nullptr, d.stream, pt.tab, nloc);
-        return;
-    }
-    const uint64_t res_bytes = std::min<uint64_t>(nloc * (uint64_t)crt_moduli() * 65536, 4ull << 30);
-    uint8_t* res = (uint8_t*)d.get(Device::S_ZBLK, res_bytes);
-    void* ws = d.get(Device::S_LUT3, crt_lut_bytes(std::min(m, step), n));
-    unsigned long long* rec = crt_record(d);
-    for (uint64_t s0 = 0; s0 < m; s0 += step) {
-        const uint64_t cnt = std::min(step, m - s0);
-        const int acc = accumulate || s0 > 0;
-        launch_syrk_packed_crt(packed + s0 * pitch, pitch, n, cnt, lut + 4 * s0, blocks, acc, ws, res, res_bytes, rec,
-                               d.stream, nullptr, nullptr, pt.tab, nloc);
-        launch_syrk_packed_f64_gated(packed + s0 * pitch, pitch, n, cnt, lut + 4 * s0, blocks, acc, (const int*)ws + 1,
-                                     d.stream, pt.tab, nloc);
-    }
-}
-
-static void syrk_packed_part_body(Device& d, const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m,
-                                  const float* lut, int rank, int world, void* blocks, int accumulate) {
-    if (use_bf3(SNPMI_DT_F32)) {
-        H2Lut h2;
-        const bool h = use_h2() && m > 0;
-        const uint32_t* l3 = lut_bf3(d, lut, m, h ? &h2 : nullptr);
-        launch_syrk_packed_bf3_part(packed, pitch, n, m, l3, rank, world, (float*)blocks, accumulate, d.stream,
-                                    h ? &h2 : nullptr);
-        return;
-    }
-    if (!use_two_phase(SNPMI_DT_F32, n) || m == 0) {
-        launch_syrk_packed_part(packed, pitch, n, m, lut, rank, world, blocks, accumulate, d.stream);
-        return;
-    }
-    for_z_blocks(d, packed, pitch, n, m, lut, [&](const float* Z, uint64_t ldz, uint64_t cnt, bool more) {
-        launch_syrk_dense_part(Z, ldz, n, cnt, rank, world, blocks, accumulate || more, d.stream);
-    });
+    for (uint64_t s0 = 0; s0 < m; s0 += step)
+        launch_syrk_packed(packed + s0 * pitch, pitch, n, std::min(step, m - s0), lut + 4 * s0, SNPMI_DT_F64, o,
+                           accumulate || s0 > 0, d.stream);
 }
 // Finish a GRM held as tiles on the device: optional DiagKtoN, then K (n x n) to the host,
 // extracted in row blocks so the device never needs a second full-size K.
@@ -986,7 +954,7 @@ static bool grm_add_bed(Device& d, T* tiles, bool first, const char* path, uint6
     return grm_stream_bed<T>(d, first, path, n_iid, n_sid, count_a1, iid_idx, n_out_iid, sid_idx, n_out_sid, std_kind,
                              a, b, use_stats, stats, num_threads,
                              [&](const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t cnt, const T* lut, bool acc) {
-                                 syrk_packed_auto(d, packed, pitch, n, cnt, lut, DT<T>::v, tiles, acc);
+                                 syrk_packed_auto(d, packed, pitch, n, cnt, lut, DT<T>::v, whole_dest(tiles, n), acc);
                              });
 }
 
@@ -1086,15 +1054,14 @@ PartTables part_tables(uint64_t nb, int rank, int world) {
     return t;
 }
 
-// dense GRM operand on the device: f32 with n >= 4096 and the default variant takes the fp16x2
-// split kernel in SNP chunks of bounded stage-image scratch (falls back to the f32-MFMA
-// k_syrk256d on the device-side range flag, or when the scratch cannot be allocated)
-static void syrk_packed_auto(Device& d, const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m,
-                             const void* lut, int dt, void* tiles, int accumulate);
-
+// dense GRM operand on the device.  f32 on the default path: genotype-valued columns are re-encoded
+// as codes (hook "dense_codes"); else n >= 4096 takes the fp16x2 split kernel in SNP chunks of
+// bounded stage-image scratch (falls back to the f32-MFMA k_syrk256d on the device-side range
+// flag, or when the scratch cannot be allocated).  Everything else: launch_syrk_dense.
 static void syrk_dense_auto(Device& d, const void* Z, uint64_t ldz, uint64_t n, uint64_t m, int dt, void* tiles,
                             int accumulate) {
-    if (dt == SNPMI_DT_F32 && g_variant_syrk == 0 && m > 0 && g_dense_codes) {
+    const bool h2_path = dt == SNPMI_DT_F32 && syrk_f32_path() == F32Path::H2 && m > 0;
+    if (h2_path && g_dense_codes) {
         // genotype-valued columns (<= 4 distinct values each, e.g. a standardized SnpData): exact
         // re-encoding as codes + LUT, then the packed fp16x2 SYRK; one host sync for the flag
         const uint64_t pitch = packed_pitch(n);
@@ -1106,11 +1073,11 @@ static void syrk_dense_auto(Device& d, const void* Z, uint64_t ldz, uint64_t n, 
         SNPMI_HIP(hipMemcpyAsync(&f, flag, sizeof(f), hipMemcpyDeviceToHost, d.stream));
         SNPMI_HIP(hipStreamSynchronize(d.stream));
         if (f == 0) {
-            syrk_packed_auto(d, packed, pitch, n, m, lut, dt, tiles, accumulate);
+            syrk_packed_auto(d, packed, pitch, n, m, lut, dt, whole_dest(tiles, n), accumulate);
             return;
         }
     }
-    if (dt == SNPMI_DT_F32 && g_variant_syrk == 0 && n >= 4096 && m > 0 && ldz % 256 == 0) {
+    if (h2_path && n >= 4096 && ldz % 256 == 0) {
         const uint64_t nb = ldz / 256;
         const uint64_t scratch = round_up(dense_h2_scratch_bytes(n, m), 256);
         uint16_t* img = nullptr;
@@ -1277,7 +1244,7 @@ static void grm_add_packed_impl(const uint8_t* packed, uint64_t pitch, uint64_t 
         if (host_stats && use_stats)
             SNPMI_HIP(hipMemcpyAsync(st, stats + 2 * s0, cnt * 2 * sizeof(T), hipMemcpyHostToDevice, d.stream));
         launch_snp_stats(src, pitch, n, cnt, count_a1, std_kind, a, b, use_stats, DT<T>::v, st, lut, d.stream);
-        syrk_packed_auto(d, src, pitch, n, cnt, lut, DT<T>::v, tiles, g_session.wrote ? 1 : 0);
+        syrk_packed_auto(d, src, pitch, n, cnt, lut, DT<T>::v, whole_dest(tiles, n), g_session.wrote ? 1 : 0);
         g_session.wrote = true;
         if (host_stats && !use_stats) {
             SNPMI_HIP(hipMemcpyAsync(stats + 2 * s0, st, cnt * 2 * sizeof(T), hipMemcpyDeviceToHost, d.stream));
@@ -1328,6 +1295,7 @@ static int g_last_groups = 0;  // column groups of the last overlapped collectiv
 // their number and a hash of their element ranges -- tests check every rank issues the same ones)
 static int g_last_sum_calls = 0;
 static uint64_t g_last_sum_sig = 0;
+static int g_last_sum_sig31 = 0;  // its low 31 bits, as the hook reports them
 
 struct OverlapSums {
     Device& d;
@@ -1335,7 +1303,11 @@ struct OverlapSums {
     std::vector<hipEvent_t> evs;
     OverlapSums(Device& dev, int coll, int rt, int dt) : d(dev), collective(coll), root(rt), dtype(dt) {
         g_last_sum_calls = 0;
-        g_last_sum_sig = 1469598103934665603ull;
+        set_sig(1469598103934665603ull);
+    }
+    static void set_sig(uint64_t s) {
+        g_last_sum_sig = s;
+        g_last_sum_sig31 = (int)(s & 0x7fffffff);
     }
     ~OverlapSums() {
         for (hipEvent_t e : evs) (void)hipEventDestroy(e);
@@ -1354,7 +1326,7 @@ struct OverlapSums {
         const uint64_t e0 = T(t0), e1 = T(t1);
         if (e1 <= e0) return;
         g_last_sum_calls++;
-        g_last_sum_sig = (g_last_sum_sig ^ (e0 * 0x9E3779B97F4A7C15ull + e1)) * 1099511628211ull;
+        set_sig((g_last_sum_sig ^ (e0 * 0x9E3779B97F4A7C15ull + e1)) * 1099511628211ull);
         hipEvent_t e = event();
         SNPMI_HIP(hipEventRecord(e, d.stream));
         SNPMI_HIP(hipStreamWaitEvent(d.aux, e, 0));
@@ -1374,7 +1346,7 @@ struct OverlapSums {
 // calls.  The split-K check uses the largest chunk: a chunk of fewer SNPs only narrows
 // the slice counts bf3_split_slices may choose, so "no split at 65536" holds for every chunk.
 static bool f32_groupable(Device& d, uint64_t n, int parts) {
-    return n > 0 && use_bf3(SNPMI_DT_F32) && use_h2() && g_diag_exact && parts > 1 &&
+    return n > 0 && syrk_f32_path() == F32Path::H2 && g_diag_exact && parts > 1 &&
            bf3_split_slices(n, 1ull << 16, d.cu_count) == 1 && ceil_div(n, 256) < 65536;
 }
 
@@ -1397,7 +1369,7 @@ static SumPlan sum_plan(Device& d, uint64_t n, int dtype, int parts) {
     if (dtype == SNPMI_DT_F32 && f32_groupable(d, n, parts)) {
         for (const auto& g : column_groups(ceil_div(n, 256), parts)) p.ranges.push_back({2 * g.c0, 2 * g.c1});
         p.grouped = true;
-    } else if (dtype == SNPMI_DT_F64 && use_crt(SNPMI_DT_F64) && n > 0) {
+    } else if (dtype == SNPMI_DT_F64 && syrk_f64_path() == F64Path::CRT && n > 0) {
         for (const auto& c : crt_column_chunks(n, crt_res_bytes(n))) p.ranges.push_back({2 * c.first, 2 * c.second});
         p.grouped = true;
     } else {
@@ -1447,9 +1419,10 @@ static int grouped_reduce_f32(Device& d, const uint8_t* src, uint64_t pitch, uin
 static int crt_reduce_f64(Device& d, const uint8_t* src, uint64_t pitch, uint64_t n, uint64_t cnt, const double* lut,
                           double* tiles, int acc, int collective, int rt, hipEvent_t syrk_done) {
     const uint64_t step = crt_max_snps();
+    const GrmDest o = whole_dest(tiles, n);
     if (cnt > step) {  // the leading SNPs the plain way, the last <= step overlapped
         const uint64_t lead = ((cnt - 1) / step) * step;
-        syrk_packed_crt(d, src, pitch, n, lead, lut, tiles, acc);
+        syrk_packed_crt(d, src, pitch, n, lead, lut, o, acc);
         src += lead * pitch;
         lut += 4 * lead;
         cnt -= lead;
@@ -1463,7 +1436,7 @@ static int crt_reduce_f64(Device& d, const uint8_t* src, uint64_t pitch, uint64_
     OverlapSums sums(d, collective, rt, SNPMI_DT_F64);
     size_t groups = 0;
     const std::function<void()> pre = [&] {
-        launch_syrk_packed_f64_gated(src, pitch, n, cnt, lut, tiles, acc, (const int*)ws + 1, d.stream);
+        launch_syrk_packed(src, pitch, n, cnt, lut, SNPMI_DT_F64, o, acc, d.stream, (const int*)ws + 1);
     };
     const std::function<void(uint64_t, uint64_t)> after = [&](uint64_t c0, uint64_t c1) {
         SNPMI_REQUIRE(groups < plan.ranges.size() && plan.ranges[groups] == std::make_pair(2 * c0, 2 * c1),
@@ -1512,10 +1485,8 @@ static void grm_add_packed_reduce_impl(const uint8_t* packed, uint64_t pitch, ui
     check_reduce_args<T>(collective, parts);
     Device& d = device();
     const int rt = collective == 1 ? root : -1;
-    const bool f64 = DT<T>::v == SNPMI_DT_F64;
     const uint64_t nchunk = m ? ceil_div(m, 1ull << 16) : 1;
     const uint64_t step = std::min<uint64_t>(1ull << 16, round_up(ceil_div(m, nchunk), 256));
-    (void)f64;
     const bool grouped = m > 0 && n > 0 && n == g_session.n && sum_plan(d, n, DT<T>::v, parts).grouped &&
                          (std_kind == SNPMI_STD_NONE || (stats && is_device_ptr(d, stats)));
     g_last_groups = 1;
@@ -1575,7 +1546,7 @@ static void grm_add_bed_reduce_impl(const char* path, uint64_t n_iid, uint64_t n
                                                 nullptr);
                 return;
             }
-            syrk_packed_auto(d, packed, pitch, nn, cnt, lut, DT<T>::v, tiles, acc);
+            syrk_packed_auto(d, packed, pitch, nn, cnt, lut, DT<T>::v, whole_dest(tiles, nn), acc);
             if (last && collective) sum_by_plan(d, plan, tiles, n, collective, rt, DT<T>::v);
         });
     g_last_groups = groups;
@@ -1659,71 +1630,83 @@ int snpmi_device_ids(int dev, uint8_t* uuid16, int* pci, int* clock_khz) {
     });
 }
 
+// The tuning / test hooks: name, where the value lives, what a set does with a value.  ANY keeps
+// it, BOOL stores value != 0, CLAMP0 stores max(value, 0), RANGE / LIST reject a value outside
+// [lo, hi] / {list} with `what` (the stored value is then unchanged), READ_ONLY rejects every set.
+struct Hook {
+    const char* name;
+    int* value;
+    enum Kind { ANY, BOOL, CLAMP0, RANGE, LIST, READ_ONLY } kind;
+    int lo, hi;  // RANGE
+    std::vector<int> list;
+    const char* what;  // RANGE / LIST: the accepted values, for the error message
+};
+static const std::vector<Hook>& hooks() {
+    static const std::vector<Hook> table = {
+        // launch_snp_stats: 6 = one wave per SNP, 7 / 9 = 4 / 16 loads in flight, 8 = 2 waves per SNP;
+        // launch_decode: 2 = no 16-B row-tile kernel, 3 = the 64x64 LDS-tile kernel;
+        // launch_decode_std_fused: 1 = the two-kernel form; launch_repack_plan: 8 = no windows,
+        // 9 / 10 = chunks of 16384 / 4096 codes, 11 = two columns per group, 17 = dword-per-lane gather
+        {"decode", &g_variant_decode, Hook::ANY, 0, 0, {}, nullptr},
+        // dense standardize: 0 = k_std_cols_f / k_std_cols_c16, 1 = round 3's kernels
+        {"std", &g_variant_std, Hook::ANY, 0, 0, {}, nullptr},
+        // 1 = exact f64 diagonal around every f32 SYRK (k_diag_*), 0 = the SYRK's own diagonal
+        {"diag", &g_diag_exact, Hook::BOOL, 0, 0, {}, nullptr},
+        // whole-K extraction: 0 = k_grm_extract_sym, 1 = k_grm_extract_rows, 2-4 = other block
+        // shapes, 5-7 = the pipelined kernel in three shapes
+        {"extract", &g_variant_extract, Hook::ANY, 0, 0, {}, nullptr},
+        // the shipped default chain and the kernels it falls back to (syrk_f32_path / syrk_f64_path):
+        // 0 = default; 36 = the bf16x3 kernel alone (fp16x2 range fallback), f64 fused; 20 = 71 = the
+        // two-phase f32 / f64 MFMA kernels (dense-operand range fallback; the CRT path's non-finite
+        // fallback is the fused f64 kernel); 5 = the fused 128x128 kernels at every N.  The shipped
+        // forms' own A/B switches are the hooks "h2" and "crt".
+        {"syrk", &g_variant_syrk, Hook::LIST, 0, 0, {0, 5, 20, 36, 71}, "syrk variant: a shipped kernel (0, 5, 20, 36, 71)"},
+        // split-K of the default f32 chain: 0 = auto (bf3_split_slices), 1 = off, S = S slices
+        {"syrk_split", &g_variant_syrk_split, Hook::ANY, 0, 0, {}, nullptr},
+        // dense fp16x2 SYRK: SNPs per stage-image chunk, 0 = by scratch size
+        {"dense_chunk", &g_dense_chunk, Hook::CLAMP0, 0, 0, {}, nullptr},
+        // 1 = genotype-valued dense operands are re-encoded as codes + LUT, 0 = never
+        {"dense_codes", &g_dense_codes, Hook::ANY, 0, 0, {}, nullptr},
+        // SNPs per f32 accumulation segment (SegFlush), 0 = one chain per launch
+        {"seg", &g_seg_snps, Hook::CLAMP0, 0, 0, {}, nullptr},
+        // host gather of .bed columns: 0 = memcpy from the mmap, 1 = pread
+        {"gather", &g_gather, Hook::ANY, 0, 0, {}, nullptr},
+        {"h2", &g_h2_kernel, Hook::RANGE, 0, 1, {}, "h2 SYRK: 0 = k_syrk_h2, 1 = k_syrk_h2s"},
+        {"crt", &g_crt_kernel, Hook::RANGE, 0, 2, {},
+         "crt residue SYRK: 0 = k_syrk_i8r, 1 = k_syrk_i8w, 2 = k_syrk_i8w without its read order / wave priorities"},
+        {"crt_block", &g_crt_block, Hook::RANGE, 0, 1, {}, "crt moduli: 0 = launch-wide R, 1 = per 256-block"},
+        {"f64", &g_f64_mfma, Hook::RANGE, 0, 1, {}, "f64 GRM path: 0 = int8 residues + CRT, 1 = f64 MFMA"},
+        // the last K-tile collective: column groups, RCCL calls, 31 bits of the hash of their ranges
+        {"overlap_groups", &g_last_groups, Hook::READ_ONLY, 0, 0, {}, nullptr},
+        {"overlap_calls", &g_last_sum_calls, Hook::READ_ONLY, 0, 0, {}, nullptr},
+        {"overlap_sig", &g_last_sum_sig31, Hook::READ_ONLY, 0, 0, {}, nullptr},
+    };
+    return table;
+}
+static const Hook& find_hook(const char* name) {
+    for (const Hook& h : hooks())
+        if (std::strcmp(name, h.name) == 0) return h;
+    throw Error(SNPMI_E_ARG, std::string("unknown kernel ") + name);
+}
+
 int snpmi_set_kernel_variant(const char* kernel, int variant) {
     return guarded([&] {
         SNPMI_REQUIRE(kernel != nullptr, SNPMI_E_ARG, "kernel name is NULL");
-        if (std::strcmp(kernel, "decode") == 0) g_variant_decode = variant;
-        else if (std::strcmp(kernel, "std") == 0) g_variant_std = variant;
-        else if (std::strcmp(kernel, "diag") == 0) g_diag_exact = variant != 0;
-        else if (std::strcmp(kernel, "extract") == 0) g_variant_extract = variant;
-        else if (std::strcmp(kernel, "syrk") == 0) {
-            // the shipped default chain and the kernels it falls back to: 36 = the bf16x3 kernel
-            // alone (fp16x2 range fallback), 20 = the f32-MFMA kernels (dense-operand range
-            // fallback), 5 = the 128x128 small-N kernels, 71 = f64 GRMs on the f64 MFMA (the CRT
-            // path's non-finite fallback).  The A/B ablations of earlier rounds were deleted (round 6);
-            // the shipped forms' own A/B switches are the hooks "h2" and "crt".
-            SNPMI_REQUIRE(variant == 0 || variant == 5 || variant == 20 || variant == 36 || variant == 71, SNPMI_E_ARG,
-                          "syrk variant " + std::to_string(variant) + " is not a shipped kernel (0, 5, 20, 36, 71)");
-            g_variant_syrk = variant;
-        }
-        else if (std::strcmp(kernel, "syrk_split") == 0) g_variant_syrk_split = variant;
-        else if (std::strcmp(kernel, "dense_chunk") == 0) g_dense_chunk = std::max(variant, 0);
-        else if (std::strcmp(kernel, "dense_codes") == 0) g_dense_codes = variant;
-        else if (std::strcmp(kernel, "seg") == 0) g_seg_snps = std::max(variant, 0);
-        else if (std::strcmp(kernel, "gather") == 0) g_gather = variant;  // host gather A/B (0 mmap, 1 pread)
-        else if (std::strcmp(kernel, "h2") == 0) {
-            SNPMI_REQUIRE(variant == 0 || variant == 1, SNPMI_E_ARG, "h2 SYRK: 0 = k_syrk_h2, 1 = k_syrk_h2s");
-            g_h2_kernel = variant;
-        }
-        else if (std::strcmp(kernel, "crt") == 0) {
-            SNPMI_REQUIRE(variant >= 0 && variant <= 2, SNPMI_E_ARG,
-                          "crt residue SYRK: 0 = k_syrk_i8r, 1 = k_syrk_i8w, 2 = k_syrk_i8w without its read "
-                          "order / wave priorities");
-            g_crt_kernel = variant;
-        }
-        else if (std::strcmp(kernel, "crt_block") == 0) {
-            SNPMI_REQUIRE(variant == 0 || variant == 1, SNPMI_E_ARG, "crt moduli: 0 = launch-wide R, 1 = per 256-block");
-            g_crt_block = variant;
-        }
-        else if (std::strcmp(kernel, "f64") == 0) {
-            SNPMI_REQUIRE(variant == 0 || variant == 1, SNPMI_E_ARG, "f64 GRM path: 0 = int8 residues + CRT, 1 = f64 MFMA");
-            g_f64_mfma = variant;
-        }
-        else throw Error(SNPMI_E_ARG, std::string("unknown kernel ") + kernel);
+        const Hook& h = find_hook(kernel);
+        const bool ok = h.kind == Hook::RANGE  ? variant >= h.lo && variant <= h.hi
+                        : h.kind == Hook::LIST ? std::find(h.list.begin(), h.list.end(), variant) != h.list.end()
+                                               : h.kind != Hook::READ_ONLY;
+        SNPMI_REQUIRE(ok, SNPMI_E_ARG,
+                      h.what ? std::string(h.what) + " (got " + std::to_string(variant) + ")"
+                             : std::string("unknown kernel ") + kernel);
+        *h.value = h.kind == Hook::BOOL ? variant != 0 : h.kind == Hook::CLAMP0 ? std::max(variant, 0) : variant;
     });
 }
 
 int snpmi_get_kernel_variant(const char* kernel, int* variant) {
     return guarded([&] {
         SNPMI_REQUIRE(kernel != nullptr && variant != nullptr, SNPMI_E_ARG, "kernel name or output is NULL");
-        if (std::strcmp(kernel, "decode") == 0) *variant = g_variant_decode;
-        else if (std::strcmp(kernel, "std") == 0) *variant = g_variant_std;
-        else if (std::strcmp(kernel, "diag") == 0) *variant = g_diag_exact;
-        else if (std::strcmp(kernel, "overlap_groups") == 0) *variant = g_last_groups;
-        else if (std::strcmp(kernel, "overlap_calls") == 0) *variant = g_last_sum_calls;
-        else if (std::strcmp(kernel, "overlap_sig") == 0) *variant = (int)(g_last_sum_sig & 0x7fffffff);
-        else if (std::strcmp(kernel, "extract") == 0) *variant = g_variant_extract;
-        else if (std::strcmp(kernel, "syrk") == 0) *variant = g_variant_syrk;
-        else if (std::strcmp(kernel, "syrk_split") == 0) *variant = g_variant_syrk_split;
-        else if (std::strcmp(kernel, "dense_chunk") == 0) *variant = g_dense_chunk;
-        else if (std::strcmp(kernel, "dense_codes") == 0) *variant = g_dense_codes;
-        else if (std::strcmp(kernel, "seg") == 0) *variant = g_seg_snps;
-        else if (std::strcmp(kernel, "gather") == 0) *variant = g_gather;
-        else if (std::strcmp(kernel, "crt") == 0) *variant = g_crt_kernel;
-        else if (std::strcmp(kernel, "crt_block") == 0) *variant = g_crt_block;
-        else if (std::strcmp(kernel, "h2") == 0) *variant = g_h2_kernel;
-        else if (std::strcmp(kernel, "f64") == 0) *variant = g_f64_mfma;
-        else throw Error(SNPMI_E_ARG, std::string("unknown kernel ") + kernel);
+        *variant = *find_hook(kernel).value;
     });
 }
 
@@ -2321,7 +2304,7 @@ int snpmi_dev_syrk_packed(const uint8_t* packed, uint64_t pitch, uint64_t n_iid,
         std::lock_guard<std::recursive_mutex> lk(g_call_mutex);  // shared scratch slots
         SNPMI_REQUIRE(dtype == SNPMI_DT_F32 || dtype == SNPMI_DT_F64, SNPMI_E_ARG, "GRM dtype must be f32/f64");
         SNPMI_REQUIRE(pitch % 64 == 0 && pitch >= ceil_div(n_iid, 4), SNPMI_E_ARG, "pitch must be snpmi_packed_pitch");
-        syrk_packed_auto(device(), packed, pitch, n_iid, n_sid, lut, dtype, K_tiles, accumulate);
+        syrk_packed_auto(device(), packed, pitch, n_iid, n_sid, lut, dtype, whole_dest(K_tiles, n_iid), accumulate);
     });
 }
 
@@ -2399,7 +2382,8 @@ static void grm_part_bed_impl(const char* path, uint64_t n_iid, uint64_t n_sid, 
             if constexpr (std::is_same<T, double>::value)
                 syrk_packed_part_f64(d, packed, pitch, n, cnt, lut, part_rank, part_world, blocks, acc);
             else
-                syrk_packed_part_auto(d, packed, pitch, n, cnt, lut, part_rank, part_world, blocks, acc);
+                syrk_packed_auto(d, packed, pitch, n, cnt, lut, SNPMI_DT_F32,
+                                 part_dest(blocks, n, part_rank, part_world), acc);
         });
     if (!wrote) SNPMI_HIP(hipMemsetAsync(blocks, 0, dev_out ? nloc * 256 * 256 * sizeof(T) : bytes, d.stream));
     const size_t bb = 256 * 256 * sizeof(T);  // one block per "row" of the pinned-bounce copy
@@ -2439,8 +2423,8 @@ int snpmi_dev_syrk_packed_part(const uint8_t* packed, uint64_t pitch, uint64_t n
         std::lock_guard<std::recursive_mutex> lk(g_call_mutex);  // shared scratch slots
         SNPMI_REQUIRE(part_world >= 1 && part_rank >= 0 && part_rank < part_world, SNPMI_E_ARG, "bad partition");
         SNPMI_REQUIRE(pitch % 64 == 0 && pitch >= ceil_div(n_iid, 4), SNPMI_E_ARG, "pitch must be snpmi_packed_pitch");
-        syrk_packed_part_auto(device(), packed, pitch, n_iid, n_sid, (const float*)lut, part_rank, part_world, blocks,
-                              accumulate);
+        syrk_packed_auto(device(), packed, pitch, n_iid, n_sid, lut, SNPMI_DT_F32,
+                         part_dest(blocks, n_iid, part_rank, part_world), accumulate);
     });
 }
 

@@ -1980,7 +1980,10 @@ inline unsigned grid_for(uint64_t work, uint64_t per_block, unsigned cap = 65536
 }  // namespace
 
 // ====================================================================== launchers
-int g_variant_decode = 0;  // tuning hook (snpmi_set_kernel_variant); no variants at present
+// tuning hook "decode": 0 = the shipped forms; the launchers below read 1 (decode_std_fused: two
+// kernels), 2 / 3 (decode: no row-tile kernel / the LDS-tile kernel), 6-9 (snp_stats: waves per SNP
+// and load depth) and 8-11, 17 (repack_plan: windows, chunk size, columns per group, gather form)
+int g_variant_decode = 0;
 int g_diag_exact = 1;     // exact f32 GRM diagonal (k_diag_*), hook "diag"
 int g_variant_std = 0;      // dense standardize: 0 = k_std_cols_f / k_std_cols_c16, 1 = round 3's kernels
 // whole-K extraction: 0 = k_grm_extract_sym, 1 = round 3's k_grm_extract_rows, 2-4 = other block

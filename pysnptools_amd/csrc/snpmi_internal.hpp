@@ -120,10 +120,11 @@ void* pinned(int slot, size_t bytes);
 void release_pinned();
 
 // ------------------------------------------------------------------ kernel launchers (kernels.hip)
+// The tuning / test hooks of snpmi_set_kernel_variant live beside the code that reads them; api.hip's
+// hook table lists every one with its accepted values.
 extern int g_variant_decode;
 extern int g_variant_std;
 extern int g_variant_extract;
-extern int g_variant_syrk;
 extern int g_dense_chunk;
 extern int g_h2_kernel;  // packed fp16x2 SYRK form (hook "h2"): 0 = k_syrk_h2, 1 = warp-specialised k_syrk_h2s
 // f32 GRM accumulation segments (syrk.hip SegFlush): every `snps` SNPs a workgroup adds its MFMA
@@ -233,13 +234,35 @@ void launch_encode(const void* val, int dtype, int order_c, uint64_t ld, uint64_
                    uint8_t* packed, uint64_t pitch, unsigned int* bad_dev, hipStream_t st);  // encode.hip
 
 // ------------------------------------------------------------------ MFMA SYRK (syrk.hip)
-void launch_syrk_packed(const uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_t n_sid, const void* lut,
-                        int dtype, void* tiles, int accumulate, hipStream_t st);
+// The GRM path the hook "syrk" (and, for f64, the switch "f64") selects; api.hip decodes the stored
+// integers in these two functions and nowhere else.
+enum class F32Path {
+    H2,         // 0: fp16x2 (k_syrk_h2s / k_syrk_h2) with the bf16x3 kernel as its range fallback
+    BF3,        // 36: the bf16x3 kernel alone
+    TWO_PHASE,  // 20, 71: f32 MFMA; n >= 4096: decode to a dense Z, then k_syrk256d; below as TILE128
+    TILE128,    // 5: f32 MFMA, fused 128x128 kernel at every n (k_syrk256 for a cfg5 part)
+};
+enum class F64Path {
+    CRT,        // 0: int8 residues + CRT, f64 MFMA gated on the non-finite flag
+    TWO_PHASE,  // 20, 71, or "f64" = 1 with 0: f64 MFMA; n >= 1024: dense Z + k_syrk_glds; below fused
+    FUSED,      // 5, 36: fused f64k::k_syrk at every n
+};
+F32Path syrk_f32_path();
+F64Path syrk_f64_path();
+// Where a SYRK writes K: the upper-triangle 128x128 tile store of the whole K (tab == nullptr), or
+// the dense 256x256 blocks of one cfg5 part in the order of its layout table
+struct GrmDest {
+    void* k;
+    const uint32_t* tab;   // PartTables::tab or nullptr
+    const int32_t* dslot;  // PartTables::dslot or nullptr
+    uint64_t blocks;       // 256-iid blocks: the whole upper triangle's, or the part's
+};
 uint64_t grm_part_blocks(uint64_t n, int rank, int world);
-void launch_syrk_packed_part(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, const void* lut,
-                             int rank, int world, void* blocks, int accumulate, hipStream_t st);
-void launch_syrk_dense_part(const float* Z, uint64_t ldz, uint64_t n, uint64_t m, int rank, int world, void* blocks,
-                            int accumulate, hipStream_t st);
+// fused packed kernels on the f32 / f64 MFMA; gate (f64): run only if that device word is non-zero
+void launch_syrk_packed(const uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_t n_sid, const void* lut,
+                        int dtype, const GrmDest& o, int accumulate, hipStream_t st, const int* gate = nullptr);
+void launch_syrk_dense_part(const float* Z, uint64_t ldz, uint64_t n, uint64_t m, const GrmDest& o, int accumulate,
+                            hipStream_t st);
 void launch_syrk_dense(const void* Z, uint64_t ldz, uint64_t n_iid, uint64_t n_sid, int dtype, void* tiles,
                        int accumulate, hipStream_t st);
 // f32 GRM on the bf16 MFMA pipe (bf16x3 split, f32 accuracy); lut3 = scratch of 32 B per SNP
@@ -262,8 +285,10 @@ uint64_t dense_h2_chunk_snps(uint64_t n);
 uint64_t dense_h2_scratch_bytes(uint64_t n, uint64_t m);
 void launch_syrk_dense_h2(const float* Z, uint64_t ldz, uint64_t n, uint64_t m, uint16_t* img, uint32_t* flag,
                           const uint32_t* order, float* tiles, int accumulate, hipStream_t st);
+// the default f32 chain (h2 given) or the bf16x3 kernel alone: over a whole destination, over the
+// column group [L0, L1) of the whole K, and in split-K form
 void launch_syrk_packed_bf3(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, const uint32_t* lut3,
-                            float* tiles, int accumulate, hipStream_t st, const H2Lut* h2 = nullptr);
+                            const GrmDest& o, int accumulate, hipStream_t st, const H2Lut* h2 = nullptr);
 void launch_syrk_packed_h2_cols(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, const uint32_t* lut3,
                                 float* tiles, int accumulate, hipStream_t st, const H2Lut* h2, uint64_t L0,
                                 uint64_t L1);
@@ -297,13 +322,5 @@ void launch_syrk_packed_crt(const uint8_t* packed, uint64_t pitch, uint64_t n, u
                             const uint32_t* part_tab = nullptr, uint64_t part_blocks = 0);
 // part_tab (cfg5): tiles = the part's part_blocks dense 256x256 f64 blocks in the order of its
 // layout table (PartTables::tab); no after_chunk.
-// the f64-MFMA packed SYRK, run only when the device word *gate is non-zero (the CRT path's flag);
-// with part_tab: into the part's dense blocks (all four 128-quadrants of each)
-void launch_syrk_packed_f64_gated(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, const double* lut,
-                                  double* tiles, int accumulate, const int* gate, hipStream_t st,
-                                  const uint32_t* part_tab = nullptr, uint64_t part_blocks = 0);
-void launch_syrk_packed_bf3_part(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, const uint32_t* lut3,
-                                 int rank, int world, float* blocks, int accumulate, hipStream_t st,
-                                 const H2Lut* h2 = nullptr);
 
 }  // namespace snpmi

@@ -64,9 +64,9 @@ __device__ __forceinline__ float sel4m(uint32_t l0, uint32_t l1, uint32_t l2, ui
 // ====================================================================== f32
 namespace f32k {
 constexpr int LDA = BM;  // floats per LDS row
+constexpr int BK = 16;    // SNPs per LDS stage
 
 // dense: F-order Z, ldz % 4 == 0; thread t moves float4 #(t + 256 q) of the BK x 128 tile
-template <int BK>
 __device__ __forceinline__ void load_dense(const float* __restrict__ Z, uint64_t ldz, uint64_t kdim, uint64_t k0,
                                            uint64_t i0, uint64_t j0, float4 (&ra)[BK / 8], float4 (&rb)[BK / 8]) {
     const int t = threadIdx.x;
@@ -87,7 +87,6 @@ __device__ __forceinline__ void load_dense(const float* __restrict__ Z, uint64_t
     }
 }
 
-template <int BK>
 __device__ __forceinline__ void store_dense(float* As, float* Bs, const float4 (&ra)[BK / 8], const float4 (&rb)[BK / 8]) {
     const int t = threadIdx.x;
 #pragma unroll
@@ -106,7 +105,6 @@ struct PRegs {
     float4 lut;
 };
 
-template <int BK>
 __device__ __forceinline__ void load_packed(const uint8_t* __restrict__ P, uint64_t pitch, uint64_t kdim, uint64_t k0,
                                             uint64_t i0, uint64_t j0, const float* __restrict__ lut,
                                             PRegs (&r)[BK / 16]) {
@@ -130,7 +128,6 @@ __device__ __forceinline__ void load_packed(const uint8_t* __restrict__ P, uint6
 
 // The 4 float4 stores of a thread are rotated by (d>>1) so the 8 lanes of each
 // ds_write_b128 group hit 8 distinct 16-B bank slots (conflict-free; was 4-way).
-template <int BK>
 __device__ __forceinline__ void store_packed(float* As, float* Bs, const PRegs (&r)[BK / 16]) {
     const int t = threadIdx.x;
     const int op = t >> 7, tt = t & 127;
@@ -155,7 +152,6 @@ __device__ __forceinline__ void store_packed(float* As, float* Bs, const PRegs (
     }
 }
 
-template <int BK>
 __device__ __forceinline__ void compute(const float* As, const float* Bs, f32x16 (&acc)[2][2], int wm, int wn,
                                         int lane) {
     const int kr = lane >> 5, c = lane & 31;
@@ -173,10 +169,10 @@ __device__ __forceinline__ void compute(const float* As, const float* Bs, f32x16
     }
 }
 
-template <bool PACKED, int BK, int MINB>
-__global__ __launch_bounds__(256, MINB) void k_syrk(const void* __restrict__ src, uint64_t ld, uint64_t kdim,
-                                                    const float* __restrict__ lut, float* __restrict__ tiles,
-                                                    int accumulate) {
+template <bool PACKED>
+__global__ __launch_bounds__(256, 4) void k_syrk(const void* __restrict__ src, uint64_t ld, uint64_t kdim,
+                                                 const float* __restrict__ lut, float* __restrict__ tiles,
+                                                 int accumulate) {
     __shared__ __attribute__((aligned(16))) float lds[2][2][BK * LDA];
     uint32_t ti, tj;
     tile_coords(blockIdx.x, ti, tj);
@@ -191,26 +187,26 @@ __global__ __launch_bounds__(256, MINB) void k_syrk(const void* __restrict__ src
 
     const uint64_t nst = (kdim + BK - 1) / BK;
     float4 ra[BK / 8], rb[BK / 8];
-    PRegs rp[BK / 16 > 0 ? BK / 16 : 1];
+    PRegs rp[BK / 16];
     if constexpr (PACKED) {
-        load_packed<BK>((const uint8_t*)src, ld, kdim, 0, i0, j0, lut, rp);
-        store_packed<BK>(lds[0][0], lds[0][1], rp);
+        load_packed((const uint8_t*)src, ld, kdim, 0, i0, j0, lut, rp);
+        store_packed(lds[0][0], lds[0][1], rp);
     } else {
-        load_dense<BK>((const float*)src, ld, kdim, 0, i0, j0, ra, rb);
-        store_dense<BK>(lds[0][0], lds[0][1], ra, rb);
+        load_dense((const float*)src, ld, kdim, 0, i0, j0, ra, rb);
+        store_dense(lds[0][0], lds[0][1], ra, rb);
     }
     __syncthreads();
     for (uint64_t s = 0; s < nst; s++) {
         const int buf = s & 1;
         const bool more = s + 1 < nst;
         if (more) {
-            if constexpr (PACKED) load_packed<BK>((const uint8_t*)src, ld, kdim, (s + 1) * BK, i0, j0, lut, rp);
-            else load_dense<BK>((const float*)src, ld, kdim, (s + 1) * BK, i0, j0, ra, rb);
+            if constexpr (PACKED) load_packed((const uint8_t*)src, ld, kdim, (s + 1) * BK, i0, j0, lut, rp);
+            else load_dense((const float*)src, ld, kdim, (s + 1) * BK, i0, j0, ra, rb);
         }
-        compute<BK>(lds[buf][0], lds[buf][1], acc, wm, wn, lane);
+        compute(lds[buf][0], lds[buf][1], acc, wm, wn, lane);
         if (more) {
-            if constexpr (PACKED) store_packed<BK>(lds[buf ^ 1][0], lds[buf ^ 1][1], rp);
-            else store_dense<BK>(lds[buf ^ 1][0], lds[buf ^ 1][1], ra, rb);
+            if constexpr (PACKED) store_packed(lds[buf ^ 1][0], lds[buf ^ 1][1], rp);
+            else store_dense(lds[buf ^ 1][0], lds[buf ^ 1][1], ra, rb);
         }
         __syncthreads();
     }
@@ -279,27 +275,17 @@ __device__ __forceinline__ void epilogue(f32x16 (&acc)[4][2], float* __restrict_
         }
 }
 
-// LOCAL (cfg5, K too large to replicate): workgroup w computes block part_tab[w] of this part's
-// layout (part_layout) and writes it as a full 256x256 row-major block at tiles + w * 65536 (no
-// cross-rank reduction is needed).
-// IL: the next stage's LUT expansion + ds_write is split into 4 pieces issued between the
-// MFMA groups of the current stage (after kk = 1, 3, 5, 7) instead of after all of them.
-// ROT: odd SNP rows of the LDS panels are stored rotated by 32 floats, so the two k-rows one
-// ds_read_b32 of the MFMA A/B operands touches (lanes 0-31: row 2kk, lanes 32-63: row
-// 2kk+1; rows are 1 KiB = a multiple of the 64-bank width) land on disjoint banks.
-template <int MINB, bool LOCAL = false, bool IL = false, bool ROT = false>
-__global__ __launch_bounds__(512, MINB) void k_syrk256(const uint8_t* __restrict__ P, uint64_t pitch, uint64_t n,
-                                                      uint64_t kdim, const float* __restrict__ lut,
-                                                      float* __restrict__ tiles, int accumulate,
-                                                      const uint32_t* __restrict__ part_tab = nullptr) {
+// Packed codes, one cfg5 part (K too large to replicate; the whole-K forms of this path are the
+// 128x128 f32k::k_syrk and the two-phase k_syrk256d): workgroup w computes block part_tab[w] of the
+// part's layout (part_layout) and writes it as a full 256x256 row-major block at tiles + w * 65536
+// (no cross-rank reduction is needed).
+__global__ __launch_bounds__(512, 1) void k_syrk256(const uint8_t* __restrict__ P, uint64_t pitch, uint64_t n,
+                                                   uint64_t kdim, const float* __restrict__ lut,
+                                                   float* __restrict__ tiles, int accumulate,
+                                                   const uint32_t* __restrict__ part_tab) {
     __shared__ __attribute__((aligned(16))) float lds[2][2][BK * LDA];
-    uint32_t bi, bj;
-    if constexpr (LOCAL) {  // slot blockIdx.x of the part's layout table (part_layout)
-        bi = part_tab[blockIdx.x] & 0xffffu;
-        bj = part_tab[blockIdx.x] >> 16;
-    } else {
-        tile_coords(blockIdx.x, bi, bj);
-    }
+    // slot blockIdx.x of the part's layout table (part_layout)
+    const uint32_t bi = part_tab[blockIdx.x] & 0xffffu, bj = part_tab[blockIdx.x] >> 16;
     const uint64_t i0 = (uint64_t)bi * BW, j0 = (uint64_t)bj * BW;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave >> 2, wn = wave & 3;
@@ -326,19 +312,6 @@ __global__ __launch_bounds__(512, MINB) void k_syrk256(const uint8_t* __restrict
             l = make_float4(0.f, 0.f, 0.f, 0.f);
         }
     };
-    auto store_part = [&](float* S, int v) {
-        const uint32_t u0 = __float_as_uint(l.x), u1 = __float_as_uint(l.y), u2 = __float_as_uint(l.z),
-                       u3 = __float_as_uint(l.w);
-        const int vv = (v + (d >> 1)) & 3;
-        const uint32_t sh = 8 * vv;
-        float4 o;
-        o.x = sel4m(u0, u1, u2, u3, w, sh);
-        o.y = sel4m(u0, u1, u2, u3, w, sh + 2);
-        o.z = sel4m(u0, u1, u2, u3, w, sh + 4);
-        o.w = sel4m(u0, u1, u2, u3, w, sh + 6);
-        const int col = ROT ? ((16 * d + 4 * vv + 32 * (kq & 1)) & (LDA - 1)) : 16 * d + 4 * vv;
-        *reinterpret_cast<float4*>(S + kq * LDA + col) = o;
-    };
     auto store = [&](float* S) {
         const uint32_t u0 = __float_as_uint(l.x), u1 = __float_as_uint(l.y), u2 = __float_as_uint(l.z),
                        u3 = __float_as_uint(l.w);
@@ -351,7 +324,7 @@ __global__ __launch_bounds__(512, MINB) void k_syrk256(const uint8_t* __restrict
             o.y = sel4m(u0, u1, u2, u3, w, sh + 2);
             o.z = sel4m(u0, u1, u2, u3, w, sh + 4);
             o.w = sel4m(u0, u1, u2, u3, w, sh + 6);
-            const int col = ROT ? ((16 * d + 4 * vv + 32 * (kq & 1)) & (LDA - 1)) : 16 * d + 4 * vv;
+            const int col = 16 * d + 4 * vv;
             *reinterpret_cast<float4*>(S + kq * LDA + col) = o;
         }
     };
@@ -368,27 +341,21 @@ __global__ __launch_bounds__(512, MINB) void k_syrk256(const uint8_t* __restrict
 #pragma unroll
         for (int kk = 0; kk < BK / 2; kk++) {
             const int row = (2 * kk + kr) * LDA;
-            float a[4], b[2];
-            const int rot = ROT ? 32 * kr : 0;
+            float a[4], b[2];  // (the no-op masks, and `col` above, keep the compiled schedule as measured)
 #pragma unroll
-            for (int x = 0; x < 4; x++) a[x] = As[row + ((wm * 128 + 32 * x + rot) & (LDA - 1)) + c];
+            for (int x = 0; x < 4; x++) a[x] = As[row + ((wm * 128 + 32 * x) & (LDA - 1)) + c];
 #pragma unroll
-            for (int y = 0; y < 2; y++) b[y] = Bs[row + ((wn * 64 + 32 * y + rot) & (LDA - 1)) + c];
+            for (int y = 0; y < 2; y++) b[y] = Bs[row + ((wn * 64 + 32 * y) & (LDA - 1)) + c];
 #pragma unroll
             for (int x = 0; x < 4; x++)
 #pragma unroll
                 for (int y = 0; y < 2; y++)
                     acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[x], b[y], acc[x][y], 0, 0, 0);
-            if constexpr (IL) {
-                if (more && (kk & 1)) store_part(op ? lds[buf ^ 1][1] : lds[buf ^ 1][0], kk >> 1);
-            }
         }
-        if constexpr (!IL) {
-            if (more) store(op ? lds[buf ^ 1][1] : lds[buf ^ 1][0]);
-        }
+        if (more) store(op ? lds[buf ^ 1][1] : lds[buf ^ 1][0]);
         __syncthreads();
     }
-    epilogue<LOCAL>(acc, tiles, n, bi, bj, accumulate, lane, wm, wn, blockIdx.x);
+    epilogue<true>(acc, tiles, n, bi, bj, accumulate, lane, wm, wn, blockIdx.x);
 }
 
 // dense operand: Z (f32, F order, column k at Z + k*ldz, ldz >= round_up(n, 256), ldz % 4 == 0)
@@ -396,26 +363,17 @@ __global__ __launch_bounds__(512, MINB) void k_syrk256(const uint8_t* __restrict
 // wave-instruction moves one 1 KiB SNP row of a 256-iid panel; odd rows are rotated by 32
 // floats through the SOURCE address (the LDS image of a glds is lane-linear) so the two rows a
 // ds_read_b32 of the MFMA operands touches hit disjoint banks.  SNP rows >= kdim are zero-filled
-// by ds_write (wave-uniform branch).
-// XCD remap: the hardware deals consecutive workgroups round-robin over the 8 XCDs (each with
-// its own L2); remapping so that XCD x runs a contiguous range of the block list keeps blocks
-// that share a panel (same column bj, neighbouring bi) on one L2 (bijective for any count).
-__device__ __forceinline__ uint64_t xcd_remap(uint64_t orig, uint64_t nwg) {
-    const uint64_t q = nwg / 8, r = nwg % 8, xcd = orig % 8;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
-}
-
-template <bool LOCAL = false, int BKD = 16, int NBUF = 2, bool XCD = false>
+// by ds_write (wave-uniform branch).  LOCAL: the blocks of one cfg5 part, as in k_syrk256.
+template <bool LOCAL = false>
 __global__ __launch_bounds__(512, 1) void k_syrk256d(const float* __restrict__ Z, uint64_t ldz, uint64_t n,
                                                     uint64_t kdim, float* __restrict__ tiles, int accumulate,
                                                     uint32_t part_rank = 0, uint32_t part_world = 1,
                                                     const uint32_t* __restrict__ gate = nullptr,
                                                     const uint32_t* __restrict__ part_tab = nullptr) {
-    static_assert(NBUF == 2 || NBUF == 3, "2 or 3 LDS stages");
-    constexpr int G = 2 * BKD / 8;  // glds per wave per stage (8 waves, one 1 KiB row each)
-    __shared__ __attribute__((aligned(16))) float lds[NBUF][2][BKD * LDA];
+    constexpr int G = 2 * BK / 8;  // glds per wave per stage (8 waves, one 1 KiB row each)
+    __shared__ __attribute__((aligned(16))) float lds[2][2][BK * LDA];
     if (gate && *gate == 0) return;  // fallback of the dense fp16x2 kernel (range flag raised)
-    const uint64_t wg = XCD ? xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
+    const uint64_t wg = blockIdx.x;
     uint32_t bi, bj;
     if constexpr (LOCAL) {  // slot wg of the part's layout table (part_layout)
         bi = part_tab[wg] & 0xffffu;
@@ -434,12 +392,12 @@ __global__ __launch_bounds__(512, 1) void k_syrk256d(const float* __restrict__ Z
     for (int x = 0; x < 4; x++)
 #pragma unroll
         for (int y = 0; y < 2; y++) acc[x][y] = (f32x16){};
-    const uint64_t nst = (kdim + BKD - 1) / BKD;
+    const uint64_t nst = (kdim + BK - 1) / BK;
     auto issue = [&](uint64_t k0, int buf) {
 #pragma unroll
         for (int q = 0; q < G; q++) {
-            const int r = wave * G + q;  // 2*BKD rows per stage: 2 panels x BKD SNPs
-            const int panel = r / BKD, k = r % BKD;
+            const int r = wave * G + q;  // 2*BK rows per stage: 2 panels x BK SNPs
+            const int panel = r / BK, k = r % BK;
             float* dst = &lds[buf][panel][k * LDA];
             const uint64_t kk = k0 + k;
             if (kk < kdim) {
@@ -455,7 +413,7 @@ __global__ __launch_bounds__(512, 1) void k_syrk256d(const float* __restrict__ Z
         const float* As = lds[buf][0];
         const float* Bs = lds[buf][1];
 #pragma unroll
-        for (int kk = 0; kk < BKD / 2; kk++) {
+        for (int kk = 0; kk < BK / 2; kk++) {
             const int row = (2 * kk + kr) * LDA;
             const int rot = 32 * kr;
             float a[4], b[2];
@@ -470,33 +428,15 @@ __global__ __launch_bounds__(512, 1) void k_syrk256d(const float* __restrict__ Z
                     acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[x], b[y], acc[x][y], 0, 0, 0);
         }
     };
-    if constexpr (NBUF == 2) {
-        issue(0, 0);
+    issue(0, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (uint64_t s = 0; s < nst; s++) {
+        const int buf = s & 1;
+        if (s + 1 < nst) issue((s + 1) * BK, buf ^ 1);
+        compute(buf);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        for (uint64_t s = 0; s < nst; s++) {
-            const int buf = s & 1;
-            if (s + 1 < nst) issue((s + 1) * BKD, buf ^ 1);
-            compute(buf);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-        }
-    } else {
-        // 3 stages, one raw barrier per stage; a counted vmcnt leaves stage s+1 in flight
-        issue(0, 0);
-        if (nst > 1) issue(BKD, 1);
-        for (uint64_t s = 0; s < nst; s++) {
-            if (s + 1 < nst) {
-                if constexpr (G == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            } else {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            if (s + 2 < nst) issue((s + 2) * BKD, (int)((s + 2) % 3));
-            compute((int)(s % 3));
-        }
     }
     epilogue<LOCAL>(acc, tiles, n, bi, bj, accumulate, lane, wm, wn, wg);
 }
@@ -690,7 +630,7 @@ struct B3Regs {
     uint4 la, lb;  // plane LUT words: (lo0, hi0, lo1, hi1), (lo2, hi2, -, -)
 };
 
-template <bool LOCAL = false, bool XCD = false, int MODE = 5>
+template <bool LOCAL = false>
 __global__ __launch_bounds__(512, 1) void k_syrk_bf3(const uint8_t* __restrict__ P, uint64_t pitch, uint64_t n,
                                                      uint64_t kdim, const uint32_t* __restrict__ lut3,
                                                      float* __restrict__ tiles, int accumulate,
@@ -698,7 +638,6 @@ __global__ __launch_bounds__(512, 1) void k_syrk_bf3(const uint8_t* __restrict__
                                                      uint64_t kslice = 0, uint64_t slice_elems = 0,
                                                      const uint32_t* __restrict__ gate = nullptr, SegCtx seg = SegCtx(),
                                                      uint64_t wg0 = 0, const uint32_t* __restrict__ part_tab = nullptr) {
-    static_assert(MODE == 5, "k_syrk_bf3: the interleaved loader with the mid-stage barrier (MODE 5)");
     __shared__ __attribute__((aligned(16))) short lds[2 * B3_STAGE];
     if (gate && *gate == 0) return;  // fallback of k_syrk_h2: runs only when its range flag is set
     if (gridDim.y > 1) {  // split-K: slice blockIdx.y covers SNPs [y*kslice, +kslice) into its own partial K
@@ -709,7 +648,7 @@ __global__ __launch_bounds__(512, 1) void k_syrk_bf3(const uint8_t* __restrict__
         tiles += (uint64_t)blockIdx.y * slice_elems;
     }
     // wg0: first block of a column-group launch (triangular order), as in k_syrk_h2
-    const uint64_t wg = wg0 + (XCD ? xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x);
+    const uint64_t wg = wg0 + blockIdx.x;
     uint32_t bi, bj;
     if constexpr (LOCAL) {  // slot wg of the part's layout table (part_layout)
         bi = part_tab[wg] & 0xffffu;
@@ -1455,11 +1394,11 @@ __device__ __forceinline__ void store_packed(double* As, double* Bs, const PRegs
     }
 }
 
-// same, with the select done on the two 32-bit halves by v_bfi_b32 (8 VALU per value)
-// ROT: write chunk (v + (d>>1) + 4(k&1)) & 7 at step v so that each 16-lane quarter of the
-// wave hits 16 distinct 4-bank groups (row stride 288 dwords = 32 mod 64 banks; without
-// the rotation all 64 lanes of a ds_write_b128 land on 2 groups).
-template <int V0 = 0, int V1 = 8, bool ROT = false>
+// same (steps [V0, V1) of the 8), with the select done on the two 32-bit halves by v_bfi_b32 (8 VALU
+// per value); chunk (v + (d>>1) + 4(k&1)) & 7 is written at step v so that each 16-lane quarter of
+// the wave hits 16 distinct 4-bank groups (row stride 288 dwords = 32 mod 64 banks; without the
+// rotation all 64 lanes of a ds_write_b128 land on 2 groups).
+template <int V0, int V1>
 __device__ __forceinline__ void store_packed_bfi(double* As, double* Bs, const PRegs& r) {
     const int t = threadIdx.x;
     const int op = t >> 7, tt = t & 127;
@@ -1472,7 +1411,7 @@ __device__ __forceinline__ void store_packed_bfi(double* As, double* Bs, const P
         lo[c] = (uint32_t)u;
         hi[c] = (uint32_t)(u >> 32);
     }
-    const int rot = ROT ? (d >> 1) + 4 * (k & 1) : 0;
+    const int rot = (d >> 1) + 4 * (k & 1);
 #pragma unroll
     for (int v0 = V0; v0 < V1; v0++) {
         const int v = (v0 + rot) & 7;
@@ -1512,7 +1451,6 @@ __device__ __forceinline__ void compute(const double* As, const double* Bs, f64x
 
 // The stage's MFMAs with the next stage's LDS store (bfi select) spread between its MFMA groups, so
 // the select VALU issues while the wave's own MFMAs are in flight instead of after them.
-template <bool ROT = false>
 __device__ __forceinline__ void compute_store(const double* As, const double* Bs, f64x4 (&acc)[4][4], int wm, int wn,
                                               int lane, double* Ns, double* Nb, const PRegs& r, bool more) {
     const int kr = lane >> 4, c = lane & 15;
@@ -1530,10 +1468,10 @@ __device__ __forceinline__ void compute_store(const double* As, const double* Bs
 #pragma unroll
             for (int y = 0; y < 4; y++) acc[x][y] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[x], b[y], acc[x][y], 0, 0, 0);
         if (more) {
-            if (kk == 0) store_packed_bfi<0, 2, ROT>(Ns, Nb, r);
-            if (kk == 1) store_packed_bfi<2, 4, ROT>(Ns, Nb, r);
-            if (kk == 2) store_packed_bfi<4, 6, ROT>(Ns, Nb, r);
-            if (kk == 3) store_packed_bfi<6, 8, ROT>(Ns, Nb, r);
+            if (kk == 0) store_packed_bfi<0, 2>(Ns, Nb, r);
+            if (kk == 1) store_packed_bfi<2, 4>(Ns, Nb, r);
+            if (kk == 2) store_packed_bfi<4, 6>(Ns, Nb, r);
+            if (kk == 3) store_packed_bfi<6, 8>(Ns, Nb, r);
         }
     }
 }
@@ -1561,7 +1499,7 @@ __device__ __forceinline__ void epilogue(f64x4 (&acc)[4][4], double* __restrict_
 
 // f64 GRM of packed codes on the f64 MFMA (the CRT path's fallback for a non-finite LUT, and hook
 // "f64" = 1): 128x128 tiles, 4 waves; the select of stage s+1's values is interleaved with stage s's
-// MFMAs and stored bank-rotated (compute_store<true>): 60.5 TFLOP/s = 0.77 of 78.6 at N = 32768
+// MFMAs and stored bank-rotated (compute_store): 60.5 TFLOP/s = 0.77 of 78.6 at N = 32768
 // (tools/ubench.py syrk --dtype f64).  part_tab (cfg5): quadrant q of slot w of the part's layout.
 __global__ __launch_bounds__(256, 2) void k_syrk(const uint8_t* __restrict__ src, uint64_t ld, uint64_t kdim,
                                                  const double* __restrict__ lut, double* __restrict__ tiles,
@@ -1600,7 +1538,7 @@ __global__ __launch_bounds__(256, 2) void k_syrk(const uint8_t* __restrict__ src
         const int buf = s & 1;
         const bool more = s + 1 < nst;
         if (more) load_packed(src, ld, kdim, (s + 1) * BK, i0, j0, lut, rp);
-        compute_store<true>(lds[buf][0], lds[buf][1], acc, wm, wn, lane, lds[buf ^ 1][0], lds[buf ^ 1][1], rp, more);
+        compute_store(lds[buf][0], lds[buf][1], acc, wm, wn, lane, lds[buf ^ 1][0], lds[buf ^ 1][1], rp, more);
         __syncthreads();
     }
     epilogue(acc, T, ldo, accumulate, lane, wm, wn);
@@ -1655,7 +1593,6 @@ __global__ __launch_bounds__(256, 2) void k_syrk_glds(const double* __restrict__
 
 }  // namespace
 
-int g_variant_syrk = 0;  // tuning hook (snpmi_set_kernel_variant "syrk")
 // 8192: 4.9e-6 of max diag at 50k x 100k on SnpGen-shaped data (21.8% missing) for +2.2% time;
 // 4096: 2.6e-6 for +3.8%; 16384: 6.9e-6 for +1.9%; none: 3.2e-5 (profiles/r03acc, r03seg)
 int g_seg_snps = 12288;  // tuning hook "seg" (round 4: 12288 with the exact f64 diagonal, k_diag_*)
@@ -1669,53 +1606,41 @@ static void for_segments(uint64_t m, int accumulate, F&& launch) {
     for (uint64_t c0 = 0; c0 < m; c0 += seg) launch(c0, std::min(seg, m - c0), accumulate || c0 > 0);
 }
 
+// elements of K behind a destination, and the m == 0 case every launcher shares: K (+)= nothing
+static uint64_t dest_elems(const GrmDest& o, uint64_t n) {
+    return o.tab ? o.blocks * (uint64_t)(f32w::BW * f32w::BW) : n_tiles_upper(n) * BM * BM;
+}
+static void zero_unless_accumulating(const GrmDest& o, uint64_t n, int dtype, int accumulate, hipStream_t st) {
+    if (!accumulate) SNPMI_HIP(hipMemsetAsync(o.k, 0, dest_elems(o, n) * dtype_size(dtype), st));
+}
+
+// The fused packed kernels on the f32 / f64 MFMA.  f32: the 128x128 kernel (whole K; below ~4k iids
+// 256-iid blocks leave CUs idle) or k_syrk256 (a part's blocks).  f64: f64k::k_syrk, with `gate`
+// only when that device word is non-zero (the CRT path's flag; then m == 0 adds nothing).
 void launch_syrk_packed(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, const void* lut, int dtype,
-                        void* tiles, int accumulate, hipStream_t st) {
-    const uint64_t nt = n_tiles_upper(n);
-    if (nt == 0) return;
-    SNPMI_REQUIRE(nt < (1ull << 31), SNPMI_E_ARG, "too many GRM tiles for one launch");
-    if (m == 0) {
-        if (!accumulate) SNPMI_HIP(hipMemsetAsync(tiles, 0, nt * BM * BM * dtype_size(dtype), st));
-        return;
-    }
-    if (dtype == SNPMI_DT_F32) {
+                        const GrmDest& o, int accumulate, hipStream_t st, const int* gate) {
+    const bool f32 = dtype == SNPMI_DT_F32;
+    const uint64_t g = o.tab ? (f32 ? o.blocks : 4 * o.blocks) : n_tiles_upper(n);
+    if (g == 0 || (gate && m == 0)) return;
+    SNPMI_REQUIRE(g < (1ull << 31), SNPMI_E_ARG, "too many GRM tiles for one launch");
+    if (m == 0) return zero_unless_accumulating(o, n, dtype, accumulate, st);
+    if (f32) {
         const float* L = (const float*)lut;
-        float* Tt = (float*)tiles;
-        // Kernel choice (tools/ubench.py syrk, MI355X): 256x256 / 8 waves reaches 129 TFLOP/s at
-        // N=50k (82%) vs 118 for 128x128 / 4 waves; below ~4k iids the 256 tiles leave CUs idle.
-        const uint64_t nb = ceil_div(n, 256);
-        // Reached for f32 only when the product path is forced off the fp16x2/bf16x3 kernels
-        // (variant 20; below N = 4096 the 128x128 kernel, variant 5)
-        const bool big = g_variant_syrk != 5 && n >= 4096;
         for_segments(m, accumulate, [&](uint64_t c0, uint64_t cnt, int acc) {
-            if (big)
-                f32w::k_syrk256<1><<<(unsigned)(nb * (nb + 1) / 2), 512, 0, st>>>(packed + c0 * pitch, pitch, n, cnt,
-                                                                                 L + 4 * c0, Tt, acc);
+            if (o.tab)
+                f32w::k_syrk256<<<(unsigned)g, 512, 0, st>>>(packed + c0 * pitch, pitch, n, cnt, L + 4 * c0, (float*)o.k,
+                                                             acc, o.tab);
             else
-                f32k::k_syrk<true, 16, 4><<<(unsigned)nt, 256, 0, st>>>(packed + c0 * pitch, pitch, cnt, L + 4 * c0, Tt,
-                                                                       acc);
+                f32k::k_syrk<true><<<(unsigned)g, 256, 0, st>>>(packed + c0 * pitch, pitch, cnt, L + 4 * c0, (float*)o.k,
+                                                               acc);
             SNPMI_HIP(hipGetLastError());
         });
         return;
     }
-    else {
-        const double* L = (const double*)lut;
-        double* Tt = (double*)tiles;
-        // tools/ubench.py syrk --dtype f64 (N=32768, 8192 SNPs): plain loader 51.3 TFLOP/s, select
-        // interleaved with the MFMAs 56.1, that + bank-rotated LDS stores (MODE 4) 60.5 (77% of
-        // 78.6); MFMA-only ablation 71.5.
-        f64k::k_syrk<<<(unsigned)nt, 256, 0, st>>>(packed, pitch, m, L, Tt, accumulate);
-    }
-    SNPMI_HIP(hipGetLastError());
-}
-
-void launch_syrk_packed_f64_gated(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, const double* lut,
-                                  double* tiles, int accumulate, const int* gate, hipStream_t st,
-                                  const uint32_t* part_tab, uint64_t part_blocks) {
-    const uint64_t nt = part_tab ? 4 * part_blocks : n_tiles_upper(n);
-    if (nt == 0 || m == 0) return;
-    SNPMI_REQUIRE(nt < (1ull << 31), SNPMI_E_ARG, "too many GRM tiles for one launch");
-    f64k::k_syrk<<<(unsigned)nt, 256, 0, st>>>(packed, pitch, m, lut, tiles, accumulate, gate, part_tab);
+    // tools/ubench.py syrk --dtype f64 (N=32768, 8192 SNPs): plain loader 51.3 TFLOP/s, select
+    // interleaved with the MFMAs 56.1, that + bank-rotated LDS stores 60.5 (77% of 78.6); MFMA-only
+    // ablation 71.5.
+    f64k::k_syrk<<<(unsigned)g, 256, 0, st>>>(packed, pitch, m, (const double*)lut, (double*)o.k, accumulate, gate, o.tab);
     SNPMI_HIP(hipGetLastError());
 }
 
@@ -1762,23 +1687,6 @@ void part_layout(uint64_t nb, int rank, int world, std::vector<uint32_t>& tab) {
         }
 }
 
-void launch_syrk_packed_part(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, const void* lut,
-                             int rank, int world, void* blocks, int accumulate, hipStream_t st) {
-    const uint64_t nloc = grm_part_blocks(n, rank, world);
-    if (nloc == 0) return;
-    SNPMI_REQUIRE(nloc < (1ull << 31), SNPMI_E_ARG, "too many GRM blocks for one launch");
-    if (m == 0) {
-        if (!accumulate) SNPMI_HIP(hipMemsetAsync(blocks, 0, nloc * 256 * 256 * sizeof(float), st));
-        return;
-    }
-    const uint32_t* tab = part_tables(ceil_div(n, 256), rank, world).tab;
-    for_segments(m, accumulate, [&](uint64_t c0, uint64_t cnt, int acc) {
-        f32w::k_syrk256<1, true><<<(unsigned)nloc, 512, 0, st>>>(packed + c0 * pitch, pitch, n, cnt,
-                                                                 (const float*)lut + 4 * c0, (float*)blocks, acc, tab);
-        SNPMI_HIP(hipGetLastError());
-    });
-}
-
 uint64_t lut_bf3_entries(uint64_t m) { return round_up(std::max<uint64_t>(m, 1), (uint64_t)2 * f32w::BK); }
 
 void launch_lut_bf3(const float* lut, uint64_t m, uint32_t* lut3, hipStream_t st) {
@@ -1799,7 +1707,7 @@ void launch_lut_h2(const float* lut, uint64_t m, uint32_t* lut2, uint32_t* flag,
 // SYRK streams 4.6 B per value per panel, so the ~256 blocks in flight must share panels: in the
 // plain column order they touch ~nb A panels at once, in this order 32.  xcd: workgroup w
 // runs on XCD w % 8, so each supertile's blocks are dealt out of 8 4 (bi) x 8 (bj) sub-tiles
-// round-robin -- measured within noise of the plain order (ubench variant 45), so the product
+// round-robin -- measured within noise of the plain order, so the product
 // uses the plain order.  Pure host function; the caller keeps the table on its device.
 void supertile_order(uint64_t nb, bool xcd, std::vector<uint32_t>& tab) {
     tab.clear();
@@ -1881,74 +1789,82 @@ void launch_syrk_dense_h2(const float* Z, uint64_t ldz, uint64_t n, uint64_t m, 
     });
 }
 
-void launch_syrk_packed_bf3(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, const uint32_t* lut3,
-                            float* tiles, int accumulate, hipStream_t st, const H2Lut* h2) {
-    const uint64_t nb = ceil_div(n, 256), g = nb * (nb + 1) / 2;
-    if (g == 0) return;
-    SNPMI_REQUIRE(g < (1ull << 31), SNPMI_E_ARG, "too many GRM blocks for one launch");
-    SNPMI_REQUIRE(pitch % 64 == 0 && pitch * 4 >= nb * 256, SNPMI_E_ARG, "packed pitch must cover round_up(n, 256) iids");
-    if (m == 0) {
-        if (!accumulate) SNPMI_HIP(hipMemsetAsync(tiles, 0, n_tiles_upper(n) * BM * BM * sizeof(float), st));
-        return;
-    }
-    // MI355X, N=50k, 10k SNPs (tools/ubench.py syrk, 7 interleaved rounds, profiles/r01g):
-    // loader interleaved between the MFMA groups (MODE 1, now 33) 302.9 TFLOP/s, + XCD remap (32)
-    // 303.3, expansion after the MFMAs (30) 306.6, + XCD remap (31) 305.3 -- equal within run
-    // noise; 39 (no loader, ablation) 380-382, at a 8% higher clock (PMC GRBM_GUI_ACTIVE).
-    // Default MODE 2 (mid-stage barrier, next B planes prefetched into registers): 311.0 vs
-    // 307.1 for MODE 1 at N=50k, 304.1 vs 300.5 at N=30k (profiles/r01i/ubench_syrk_bf3_mode2.jsonl);
-    // SIMD partners staggered by one loader slot (waves 4-7 expand before group 0, runtime
-    // plane index, 3 VGPRs spilled) lost: 296.8 vs 313.5 (ubench_syrk_bf3_stagger.jsonl).
-    if (h2) {
-        // MI355X, N=50k, 10k SNPs (tools/ubench.py syrk, profiles/r01j/ubench_syrk_h2_modes.jsonl):
-        // 32-SNP stages, compiler-ordered loader (MODE 4) 577 TFLOP/s; 16-SNP stages 505-564;
-        // bf16x3 300-313.  Round 6: the loader in its own waves (k_syrk_h2s) 256.6 vs 270.0 ms per
-        // 50k x 62.5k launch (profiles/r06g).  Supertile block order: the ~256 blocks in flight share
-        // ~32 code panels instead of ~nb (+1.7-2.4% vs the triangular order, profiles/r03crt).
+// The default f32 chain, launched from this one place: the fp16x2 kernel (k_syrk_h2s, or k_syrk_h2
+// by hook "h2") and the bf16x3 kernel gated on its range flag; h2 == nullptr: the bf16x3 kernel
+// alone.  Grid x = blocks [L0, L1) of `table` (LOCAL: the part's layout table, which is also the
+// storage order; else the supertile order of the fp16x2 kernels, while the bf16x3 kernel walks the
+// triangle -- both keep their full-grid block identity through wg0 = L0).  slices > 1 (grid y):
+// slice y covers SNPs [y * kslice, + kslice) into dst + y * slice_elems.
+// MI355X, N=50k, 10k SNPs (tools/ubench.py syrk): fp16x2 with 32-SNP stages 577 TFLOP/s, 16-SNP
+// stages 505-564, bf16x3 300-313 (profiles/r01j/ubench_syrk_h2_modes.jsonl); the loader in its own
+// waves (k_syrk_h2s) 256.6 vs 270.0 ms per 50k x 62.5k launch (profiles/r06g); supertile block
+// order: the ~256 blocks in flight share ~32 code panels instead of ~nb (+1.7-2.4% vs the
+// triangular order, profiles/r03crt).  bf16x3 with the mid-stage barrier and the next B planes
+// prefetched into registers: 311.0 vs 307.1 for the loader interleaved between the MFMA groups at
+// N=50k, 304.1 vs 300.5 at N=30k (profiles/r01i/ubench_syrk_bf3_mode2.jsonl).
+struct F32Chain {
+    uint64_t L0, L1;
+    unsigned slices;
+    uint64_t kslice, slice_elems;
+    float* dst;
+    const uint32_t* table;
+    const H2Lut* h2;
+};
+
+template <bool LOCAL>
+static void launch_f32_chain(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, const uint32_t* lut3,
+                             const F32Chain& c, int accumulate, hipStream_t st) {
+    const dim3 grid((unsigned)(c.L1 - c.L0), c.slices);
+    const SegCtx seg = seg_ctx();
+    if (c.h2) {
         if (g_h2_kernel == 1)
-            f32w::k_syrk_h2s<false><<<(unsigned)g, 768, 0, st>>>(packed, pitch, n, m, h2->lut2, h2->flag, tiles,
-                                                                accumulate, 0, 1, 0, 0, seg_ctx(),
-                                                                packed_block_order(ceil_div(n, 256)));
+            f32w::k_syrk_h2s<LOCAL><<<grid, 768, 0, st>>>(packed, pitch, n, m, c.h2->lut2, c.h2->flag, c.dst, accumulate,
+                                                         0, 1, c.kslice, c.slice_elems, seg, c.table, c.L0);
         else
-            f32w::k_syrk_h2<false, 4><<<(unsigned)g, 512, 0, st>>>(packed, pitch, n, m, h2->lut2, h2->flag, tiles,
-                                                                  accumulate, 0, 1, 0, 0, seg_ctx(),
-                                                                  packed_block_order(ceil_div(n, 256)));
+            f32w::k_syrk_h2<LOCAL><<<grid, 512, 0, st>>>(packed, pitch, n, m, c.h2->lut2, c.h2->flag, c.dst, accumulate,
+                                                        0, 1, c.kslice, c.slice_elems, seg, c.table, c.L0);
         SNPMI_HIP(hipGetLastError());
-        f32w::k_syrk_bf3<false, false, 5><<<(unsigned)g, 512, 0, st>>>(packed, pitch, n, m, lut3, tiles, accumulate, 0, 1, 0, 0,
-                                                                      h2->flag, seg_ctx());
-        SNPMI_HIP(hipGetLastError());
-        return;
     }
-    f32w::k_syrk_bf3<false, false, 5><<<(unsigned)g, 512, 0, st>>>(packed, pitch, n, m, lut3, tiles, accumulate, 0, 1, 0,
-                                                                  0, nullptr, seg_ctx());
+    f32w::k_syrk_bf3<LOCAL><<<grid, 512, 0, st>>>(packed, pitch, n, m, lut3, c.dst, accumulate, 0, 1, c.kslice,
+                                                 c.slice_elems, c.h2 ? c.h2->flag : nullptr, seg, c.L0,
+                                                 LOCAL ? c.table : nullptr);
     SNPMI_HIP(hipGetLastError());
+}
+
+static void check_chain_pitch(uint64_t pitch, uint64_t n) {
+    SNPMI_REQUIRE(pitch % 64 == 0 && pitch * 4 >= ceil_div(n, 256) * 256, SNPMI_E_ARG,
+                  "packed pitch must cover round_up(n, 256) iids");
+}
+
+// the chain over all of a destination's blocks
+void launch_syrk_packed_bf3(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, const uint32_t* lut3,
+                            const GrmDest& o, int accumulate, hipStream_t st, const H2Lut* h2) {
+    if (o.blocks == 0) return;
+    SNPMI_REQUIRE(o.blocks < (1ull << 31), SNPMI_E_ARG, "too many GRM blocks for one launch");
+    check_chain_pitch(pitch, n);
+    if (m == 0) return zero_unless_accumulating(o, n, SNPMI_DT_F32, accumulate, st);
+    if (o.tab)
+        launch_f32_chain<true>(packed, pitch, n, m, lut3, {0, o.blocks, 1, 0, 0, (float*)o.k, o.tab, h2}, accumulate, st);
+    else
+        launch_f32_chain<false>(packed, pitch, n, m, lut3,
+                                {0, o.blocks, 1, 0, 0, (float*)o.k, h2 ? packed_block_order(ceil_div(n, 256)) : nullptr, h2},
+                                accumulate, st);
 }
 
 // One column group of the default f32 SYRK: the upper-triangle 256-blocks [L0, L1) -- whole
 // supertile columns, so the same blocks sit at [L0, L1) of both the supertile table (k_syrk_h2)
-// and the triangular order (the bf16x3 range fallback) -- each kernel with its full-grid block
-// identity (wg0 = L0), so a launch split into column groups writes the same K bit for bit as the
-// whole launch.  Used to overlap the K-tile collective of finished groups with the next group's
-// SYRK (api.hip grm_add_packed_reduce).
+// and the triangular order (the bf16x3 range fallback) -- so a launch split into column groups
+// writes the same K bit for bit as the whole launch.  Used to overlap the K-tile collective of
+// finished groups with the next group's SYRK (api.hip grm_add_packed_reduce).
 void launch_syrk_packed_h2_cols(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, const uint32_t* lut3,
                                 float* tiles, int accumulate, hipStream_t st, const H2Lut* h2, uint64_t L0,
                                 uint64_t L1) {
     const uint64_t nb = ceil_div(n, 256), g = nb * (nb + 1) / 2;
     SNPMI_REQUIRE(h2 && L0 < L1 && L1 <= g && g < (1ull << 31), SNPMI_E_ARG, "bad SYRK column group");
-    SNPMI_REQUIRE(pitch % 64 == 0 && pitch * 4 >= nb * 256, SNPMI_E_ARG, "packed pitch must cover round_up(n, 256) iids");
+    check_chain_pitch(pitch, n);
     if (m == 0) return;
-    if (g_h2_kernel == 1)
-        f32w::k_syrk_h2s<false><<<(unsigned)(L1 - L0), 768, 0, st>>>(packed, pitch, n, m, h2->lut2, h2->flag, tiles,
-                                                                    accumulate, 0, 1, 0, 0, seg_ctx(),
-                                                                    packed_block_order(nb), L0);
-    else
-        f32w::k_syrk_h2<false, 4><<<(unsigned)(L1 - L0), 512, 0, st>>>(packed, pitch, n, m, h2->lut2, h2->flag, tiles,
-                                                                      accumulate, 0, 1, 0, 0, seg_ctx(),
-                                                                      packed_block_order(nb), L0);
-    SNPMI_HIP(hipGetLastError());
-    f32w::k_syrk_bf3<false, false, 5><<<(unsigned)(L1 - L0), 512, 0, st>>>(packed, pitch, n, m, lut3, tiles, accumulate,
-                                                                          0, 1, 0, 0, h2->flag, seg_ctx(), L0);
-    SNPMI_HIP(hipGetLastError());
+    launch_f32_chain<false>(packed, pitch, n, m, lut3, {L0, L1, 1, 0, 0, tiles, packed_block_order(nb), h2}, accumulate,
+                            st);
 }
 
 // split-K form for grids too small to fill the chip (N <~ 16k): `slices` partial tile sets in
@@ -1961,68 +1877,27 @@ void launch_syrk_packed_bf3_split(const uint8_t* packed, uint64_t pitch, uint64_
     const uint64_t kslice = round_up(ceil_div(m, (uint64_t)slices), (uint64_t)2 * f32w::BK);
     const unsigned S = (unsigned)ceil_div(m, kslice);
     SNPMI_REQUIRE(g < (1ull << 31) && S >= 1, SNPMI_E_ARG, "bad split");
-    if (h2) {
-        if (g_h2_kernel == 1)
-            f32w::k_syrk_h2s<><<<dim3((unsigned)g, S), 768, 0, st>>>(packed, pitch, n, m, h2->lut2, h2->flag, partial, 0, 0,
-                                                                    1, kslice, elems, seg_ctx(), packed_block_order(nb));
-        else
-            f32w::k_syrk_h2<><<<dim3((unsigned)g, S), 512, 0, st>>>(packed, pitch, n, m, h2->lut2, h2->flag, partial, 0, 0,
-                                                                   1, kslice, elems, seg_ctx(), packed_block_order(nb));
-        SNPMI_HIP(hipGetLastError());
-    }
-    f32w::k_syrk_bf3<false, false, 5><<<dim3((unsigned)g, S), 512, 0, st>>>(packed, pitch, n, m, lut3, partial, 0, 0, 1,
-                                                                          kslice, elems, h2 ? h2->flag : nullptr,
-                                                                          seg_ctx());
-    SNPMI_HIP(hipGetLastError());
+    launch_f32_chain<false>(packed, pitch, n, m, lut3,
+                            {0, g, S, kslice, elems, partial, h2 ? packed_block_order(nb) : nullptr, h2}, 0, st);
     launch_tile_reduce(partial, S, elems, tiles, accumulate, st);
 }
 
-void launch_syrk_packed_bf3_part(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, const uint32_t* lut3,
-                                 int rank, int world, float* blocks, int accumulate, hipStream_t st,
-                                 const H2Lut* h2) {
-    const uint64_t nloc = grm_part_blocks(n, rank, world);
-    if (nloc == 0) return;
-    SNPMI_REQUIRE(nloc < (1ull << 31), SNPMI_E_ARG, "too many GRM blocks for one launch");
-    SNPMI_REQUIRE(pitch % 64 == 0 && pitch * 4 >= ceil_div(n, 256) * 256, SNPMI_E_ARG,
-                  "packed pitch must cover round_up(n, 256) iids");
-    if (m == 0) {
-        if (!accumulate) SNPMI_HIP(hipMemsetAsync(blocks, 0, nloc * 256 * 256 * sizeof(float), st));
-        return;
-    }
-    const uint32_t* tab = part_tables(ceil_div(n, 256), rank, world).tab;
-    if (h2) {
-        if (g_h2_kernel == 1)
-            f32w::k_syrk_h2s<true><<<(unsigned)nloc, 768, 0, st>>>(packed, pitch, n, m, h2->lut2, h2->flag, blocks,
-                                                                  accumulate, 0, 1, 0, 0, seg_ctx(), tab);
-        else
-            f32w::k_syrk_h2<true><<<(unsigned)nloc, 512, 0, st>>>(packed, pitch, n, m, h2->lut2, h2->flag, blocks,
-                                                                  accumulate, 0, 1, 0, 0, seg_ctx(), tab);
-        SNPMI_HIP(hipGetLastError());
-    }
-    f32w::k_syrk_bf3<true, false, 5><<<(unsigned)nloc, 512, 0, st>>>(packed, pitch, n, m, lut3, blocks, accumulate,
-                                                                     0, 1, 0, 0, h2 ? h2->flag : nullptr, seg_ctx(),
-                                                                     0, tab);
-    SNPMI_HIP(hipGetLastError());
-}
-
-void launch_syrk_dense_part(const float* Z, uint64_t ldz, uint64_t n, uint64_t m, int rank, int world, void* blocks,
-                            int accumulate, hipStream_t st) {
-    const uint64_t nloc = grm_part_blocks(n, rank, world);
-    if (nloc == 0) return;
-    SNPMI_REQUIRE(nloc < (1ull << 31), SNPMI_E_ARG, "too many GRM blocks for one launch");
+// dense f32 operand into one cfg5 part's blocks (the second phase of the two-phase path)
+void launch_syrk_dense_part(const float* Z, uint64_t ldz, uint64_t n, uint64_t m, const GrmDest& o, int accumulate,
+                            hipStream_t st) {
+    if (o.blocks == 0) return;
+    SNPMI_REQUIRE(o.blocks < (1ull << 31), SNPMI_E_ARG, "too many GRM blocks for one launch");
     SNPMI_REQUIRE(ldz % 4 == 0 && ldz >= ceil_div(n, 256) * 256, SNPMI_E_ARG, "dense GRM operand needs ldz >= round_up(n, 256)");
-    if (m == 0) {
-        if (!accumulate) SNPMI_HIP(hipMemsetAsync(blocks, 0, nloc * 256 * 256 * sizeof(float), st));
-        return;
-    }
-    const uint32_t* tab = part_tables(ceil_div(n, 256), rank, world).tab;
+    if (m == 0) return zero_unless_accumulating(o, n, SNPMI_DT_F32, accumulate, st);
     for_segments(m, accumulate, [&](uint64_t c0, uint64_t cnt, int acc) {
-        f32w::k_syrk256d<true><<<(unsigned)nloc, 512, 0, st>>>(Z + c0 * ldz, ldz, n, cnt, (float*)blocks, acc, 0, 1,
-                                                               nullptr, tab);
+        f32w::k_syrk256d<true><<<(unsigned)o.blocks, 512, 0, st>>>(Z + c0 * ldz, ldz, n, cnt, (float*)o.k, acc, 0, 1,
+                                                                   nullptr, o.tab);
         SNPMI_HIP(hipGetLastError());
     });
 }
 
+// dense operand (F order, padded ldz) on the f32 / f64 MFMA, whole K: k_syrk256d at n >= 4096 unless
+// the hook asks for the 128x128 kernel; f64: k_syrk_glds
 void launch_syrk_dense(const void* Z, uint64_t ldz, uint64_t n, uint64_t m, int dtype, void* tiles, int accumulate,
                        hipStream_t st) {
     const uint64_t nt = n_tiles_upper(n);
@@ -2033,26 +1908,22 @@ void launch_syrk_dense(const void* Z, uint64_t ldz, uint64_t n, uint64_t m, int 
         if (!accumulate) SNPMI_HIP(hipMemsetAsync(tiles, 0, nt * BM * BM * dtype_size(dtype), st));
         return;
     }
-    if (dtype == SNPMI_DT_F32) {
-        const uint64_t nb = ceil_div(n, 256);
-        const unsigned g = (unsigned)(nb * (nb + 1) / 2);
-        const float* Zf = (const float*)Z;
-        float* Tf = (float*)tiles;
-        if (n >= 4096 && ldz >= nb * 256 && g_variant_syrk != 5)
-            for_segments(m, accumulate, [&](uint64_t c0, uint64_t cnt, int acc) {
-                f32w::k_syrk256d<><<<g, 512, 0, st>>>(Zf + c0 * ldz, ldz, n, cnt, Tf, acc);
-                SNPMI_HIP(hipGetLastError());
-            });
-        else
-            for_segments(m, accumulate, [&](uint64_t c0, uint64_t cnt, int acc) {
-                f32k::k_syrk<false, 16, 4><<<(unsigned)nt, 256, 0, st>>>(Zf + c0 * ldz, ldz, cnt, nullptr, Tf, acc);
-                SNPMI_HIP(hipGetLastError());
-            });
-    }
-    else {
+    if (dtype == SNPMI_DT_F64) {
         f64k::k_syrk_glds<<<(unsigned)nt, 256, 0, st>>>((const double*)Z, ldz, m, (double*)tiles, accumulate);
+        SNPMI_HIP(hipGetLastError());
+        return;
     }
-    SNPMI_HIP(hipGetLastError());
+    const uint64_t nb = ceil_div(n, 256);
+    const float* Zf = (const float*)Z;
+    float* Tf = (float*)tiles;
+    const bool wide = n >= 4096 && ldz >= nb * 256 && syrk_f32_path() != F32Path::TILE128;
+    for_segments(m, accumulate, [&](uint64_t c0, uint64_t cnt, int acc) {
+        if (wide)
+            f32w::k_syrk256d<><<<(unsigned)(nb * (nb + 1) / 2), 512, 0, st>>>(Zf + c0 * ldz, ldz, n, cnt, Tf, acc);
+        else
+            f32k::k_syrk<false><<<(unsigned)nt, 256, 0, st>>>(Zf + c0 * ldz, ldz, cnt, nullptr, Tf, acc);
+        SNPMI_HIP(hipGetLastError());
+    });
 }
 
 }  // namespace snpmi
