@@ -269,6 +269,9 @@ int snpmi_memcpy_h2d(void* dst, const void* src, uint64_t bytes);
 int snpmi_memcpy_d2h(void* dst, const void* src, uint64_t bytes);
 /* device -> device on the library stream (asynchronous; bench.py's measured copy peak) */
 int snpmi_dev_memcpy_d2d(void* dst, const void* src, uint64_t bytes);
+/* device -> device, `rows` rows of `width` bytes at the two pitches (asynchronous, the calling
+ * thread's stream): drops the pad rows of a 16-aligned F-order decode without leaving HBM */
+int snpmi_dev_memcpy_2d(void* dst, uint64_t dpitch, const void* src, uint64_t spitch, uint64_t width, uint64_t rows);
 int snpmi_stream_sync(void);
 int snpmi_event_create(void** ev);
 int snpmi_event_destroy(void* ev);
@@ -302,6 +305,25 @@ int snpmi_dev_synth_bed(uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_
  * generator, same distribution) */
 int snpmi_host_synth_bed(uint8_t* dst, uint64_t pitch, uint64_t n_iid, uint64_t sid0, uint64_t n_sid, uint64_t seed,
                          double miss_rate, const double* maf_x, const double* maf_cdf, int n_pts, int num_threads);
+/* SnpGen (snpreader/snpgen.py:164-189): the requested SNPs' packed codes (count_A1 = False), all
+ * iids, column k of the output = SNP sid_idx[k]; every batch touched is generated once per call, bit for
+ * bit the reference's values. packed: device, [n_sel][pitch] bytes (pitch >= ceil(n_iid / 4); pad
+ * bytes are zeroed).  sid_idx (any order, repeats allowed), maf_x and maf_cdf (the MAF points and
+ * the normalised cumulative weights of RandomState.choice) are host arrays.  A batch seed
+ * seed + (sid / block_size) * block_size above 2**32 - 1 is SNPMI_E_ARG, checked before any
+ * launch.  Device scratch is per generator workgroup (about 3 * n_iid * block_size bits), as many
+ * workgroups as fit scratch_bytes (0 = 1 GiB; at least one, at most 8 per CU): it does not grow
+ * with the request.  A batch that is not full after 4096 rounds (a MAF table that yields no legal
+ * SNP) is SNPMI_E_ARG.  Synchronous. */
+int snpmi_dev_snpgen_bed(uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_t seed, uint64_t block_size,
+                         const uint64_t* sid_idx, uint64_t n_sel, const double* maf_x, const double* maf_cdf,
+                         int n_pts, uint64_t scratch_bytes);
+/* generator workgroups (batches x rounds) the calling thread's last snpmi_dev_snpgen_bed ran; each
+ * consumed 2 * block_size * (1 + 3 * n_iid) words of its stream (tools/bench_snpgen.py's rate) */
+int snpmi_dev_snpgen_rounds(uint64_t* batch_rounds);
+/* the raw stream, for pinning it to numpy: count doubles of RandomState(seed32).random_sample into
+ * device memory (one workgroup; synchronous) */
+int snpmi_dev_mt19937_random_sample(uint32_t seed32, uint64_t count, double* out_dev);
 /* selected .bed columns (all iids) into a host buffer at `pitch` bytes per column (zero pad) --
  * the gather half of the file readers (bed.py:337-343), for the cfg5 plan's per-rank shares */
 int snpmi_bed_gather_packed(const char* path, uint64_t n_iid, uint64_t n_sid, const uint64_t* sid_idx, uint64_t n_sel,

@@ -94,6 +94,7 @@ _SIGS = {
     "snpmi_memcpy_h2d": [_vp, _vp, _u64],
     "snpmi_memcpy_d2h": [_vp, _vp, _u64],
     "snpmi_dev_memcpy_d2d": [_vp, _vp, _u64],
+    "snpmi_dev_memcpy_2d": [_vp, _u64, _vp, _u64, _u64, _u64],
     "snpmi_stream_sync": [],
     "snpmi_event_create": [ctypes.POINTER(ctypes.c_void_p)],
     "snpmi_event_destroy": [_vp],
@@ -106,6 +107,9 @@ _SIGS = {
     "snpmi_event_sync": [_vp],
     "snpmi_dev_synth_bed": [_vp, _u64, _u64, _u64, _u64, _u64, _f64, _vp, _vp, _i32],
     "snpmi_host_synth_bed": [_vp, _u64, _u64, _u64, _u64, _u64, _f64, _vp, _vp, _i32, _i32],
+    "snpmi_dev_snpgen_bed": [_vp, _u64, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _i32, _u64],
+    "snpmi_dev_snpgen_rounds": [_u64p],
+    "snpmi_dev_mt19937_random_sample": [ctypes.c_uint32, _u64, _vp],
     "snpmi_bed_gather_packed": [_cp, _u64, _u64, _vp, _u64, _u64, _vp, _i32],
     "snpmi_dev_snp_stats": [_vp, _u64, _u64, _u64, _i32, _i32, _f64, _f64, _i32, _i32, _vp, _vp],
     "snpmi_dev_decode": [_vp, _u64, _u64, _u64, _vp, _i32, _i32, _vp, _u64],

@@ -2030,6 +2030,15 @@ int snpmi_memcpy_d2h(void* dst, const void* src, uint64_t bytes) {
         SNPMI_HIP(hipStreamSynchronize(stream()));
     });
 }
+int snpmi_dev_memcpy_2d(void* dst, uint64_t dpitch, const void* src, uint64_t spitch, uint64_t width, uint64_t rows) {
+    return guarded([&] {
+        SNPMI_REQUIRE(dpitch >= width && spitch >= width, SNPMI_E_ARG, "a pitch is smaller than the row width");
+        if (width == 0 || rows == 0) return;
+        SNPMI_REQUIRE(dst != nullptr && src != nullptr, SNPMI_E_ARG, "NULL argument");
+        SNPMI_HIP(hipMemcpy2DAsync(dst, dpitch, src, spitch, width, rows, hipMemcpyDeviceToDevice, stream()));
+    });
+}
+
 int snpmi_dev_memcpy_d2d(void* dst, const void* src, uint64_t bytes) {
     return guarded([&] {
         const bool aligned = reinterpret_cast<uintptr_t>(dst) % 16 == 0 && reinterpret_cast<uintptr_t>(src) % 16 == 0;

@@ -6,6 +6,8 @@
   native call, ``snpmi_grm_bed_{f32,f64}``: packed codes are uploaded once, standardized
   through per-SNP LUTs inside the MFMA SYRK staging, and K accumulates in HBM;
 * an in-memory ``SnpData`` runs ``snpmi_grm_dense_{f32,f64}`` (standardize + SYRK on the GPU);
+* a ``SnpGen`` (all iids, any SNP subset) generates packed batches in HBM and adds them to one GRM
+  session (``snpmi_dev_snpgen_bed`` + ``snpmi_grm_begin / add_packed / end``);
 * anything else (custom readers or standardizers) follows the reference's block loop,
   each block's Z Z^T still computed on the GPU.
 
@@ -208,6 +210,8 @@ def _read_bed_into_hbm(reader, order, dtype, num_threads):
     from pysnptools_amd.snpreader.bed import Bed
 
     base, rows, cols = _resolve(reader)
+    if _is_snpgen(base):
+        return _snpgen_into_hbm(base, rows, cols, order, dtype)
     if not isinstance(base, Bed):
         return None
     base._run_once()
@@ -243,6 +247,8 @@ def _read_and_standardize(reader, standardizer, order="F", dtype=np.float64, for
     dtype = np.dtype(dtype)
     args = _std_args(standardizer) if dtype in (np.float32, np.float64) else None
     base, rows, cols = _resolve(reader) if args is not None and args[0] != N.STD_NONE else (None, None, None)
+    if not force_python_only and rows is None and _is_snpgen(base):
+        return _snpgen_read_and_standardize(reader, base, cols, standardizer, args, order, dtype)
     if force_python_only or not isinstance(base, Bed):
         return reader.read(order=order, dtype=dtype).standardize(standardizer, return_trained=True,
                                                                  force_python_only=force_python_only,
@@ -265,6 +271,83 @@ def _read_and_standardize(reader, standardizer, order="F", dtype=np.float64, for
     data = SnpData(reader.iid, sid, out, pos=reader.pos, name=str(reader), xp=xp)
     data._std_string_list.append(str(standardizer))
     return data, _trained_from(standardizer, kind, a, b, sid, stats)
+
+
+# ---------------------------------------------------------------------- SnpGen: generated in HBM
+def _is_snpgen(base):
+    from pysnptools_amd.snpreader.snpgen import SnpGen
+
+    return isinstance(base, SnpGen)
+
+
+def _snpgen_cols(base, cols):
+    return np.arange(base.sid_count) if cols is None else np.asarray(cols)
+
+
+def _snpgen_into_hbm(base, rows, cols, order, dtype):
+    """``read(xp='hbm')`` of a SnpGen (or a subset of one): generated and decoded in HBM.  A float
+    iid subset is gathered there too (the sub_matrix kernel); an int8 iid subset, which that kernel
+    does not take, is sliced on the host and copied back."""
+    from pysnptools_amd import hbm
+    from pysnptools_amd.util import sub_matrix
+
+    if dtype not in (np.float32, np.float64, np.int8):
+        raise ValueError("dtype '{0}' not supported; use float32, float64 or int8".format(dtype))
+    order = "F" if order == "A" else order
+    col_index = _snpgen_cols(base, cols)
+    if rows is None:
+        return base._decode(col_index, order, dtype, to_hbm=True)
+    if dtype == np.int8 or len(rows) == 0 or len(col_index) == 0:
+        return hbm.asarray(base._read(rows, cols, order, dtype, False, False, None), order=order)
+    full = base._decode(col_index, order, dtype, to_hbm=True)
+    return sub_matrix(full, rows, np.arange(len(col_index)), order=order, dtype=dtype)
+
+
+def _snpgen_read_and_standardize(reader, base, cols, standardizer, args, order, dtype):
+    """read + standardize of an all-iid SnpGen as per-SNP stats from the code counts and a decode
+    through the per-SNP table (snpmi_dev_snp_stats + snpmi_dev_decode), the packed codes never
+    leaving HBM."""
+    from pysnptools_amd import hbm
+    from pysnptools_amd.snpreader.snpdata import SnpData
+    from pysnptools_amd.util import array_module
+
+    kind, a, b, use_stats, _, _ = args
+    sid = reader.sid
+    order = "F" if order == "A" else order
+    stats = (np.ascontiguousarray(standardizer.stats_for(sid), dtype=dtype) if use_stats
+             else np.empty((len(sid), 2), dtype=dtype))
+    xp = array_module(None)
+    out = base._decode(_snpgen_cols(base, cols), order, dtype, std=(kind, a, b, use_stats), stats=stats,
+                       to_hbm=xp is hbm)
+    data = SnpData(reader.iid, sid, out, pos=reader.pos, name=str(reader), xp=xp)
+    data._std_string_list.append(str(standardizer))
+    return data, _trained_from(standardizer, kind, a, b, sid, stats)
+
+
+def _snpgen_grm(base, cols, n, kind, a, b, use_stats, stats, diag_k_to_n, fptr, K, dtype, chunk_bytes=1 << 30):
+    """K of an all-iid SnpGen: packed batches are generated in HBM and added to the GRM session
+    (snpmi_grm_begin / add_packed / end) chunk by chunk -- the values never exist as floats and K
+    is never built from host values.  Chunks are whole batches when the SNPs are a contiguous range;
+    otherwise a batch whose SNPs fall into two chunks is generated once for each.  Every batch seed
+    is range-checked before the session opens."""
+    sfx = N.suffix(dtype)
+    col_index = _snpgen_cols(base, cols)
+    base._check_seeds(col_index)
+    pitch = int(N.lib().snpmi_packed_pitch(n))
+    bs = int(base._block_size)
+    step = max(bs, chunk_bytes // pitch // bs * bs)
+    N.call("snpmi_grm_begin", n, N.dt_code(dtype))
+    try:
+        for c0 in range(0, len(col_index), step):
+            here = slice(c0, min(c0 + step, len(col_index)))
+            packed, _ = base._packed(col_index[here])
+            st = np.ascontiguousarray(stats[here])
+            N.call("snpmi_grm_add_packed_" + sfx, N.ptr(packed), pitch, n, here.stop - here.start, 0, kind, a, b,
+                   int(use_stats), N.ptr(st))
+            if not use_stats:
+                stats[here] = st
+    finally:
+        N.call("snpmi_grm_end", int(bool(diag_k_to_n)), fptr, N.ptr(K))
 
 
 def _resolve(reader):
@@ -374,6 +457,10 @@ def _native_grm(reader, standardizer, dtype, num_threads, diag_k_to_n):
                    num_threads=num_threads, dist=group)
     if merged is not None:
         _grm_pieces(merged, rows, cols, n, kind, a, b, use_stats, stats, diag_k_to_n, fptr, K, dtype, num_threads)
+    elif _is_snpgen(base):
+        if rows is not None or (group is not None and group.world > 1):
+            return None  # iid subsets and multi-rank groups take the generic block loop
+        _snpgen_grm(base, cols, n, kind, a, b, use_stats, stats, diag_k_to_n, fptr, K, dtype)
     elif isinstance(base, Bed):
         base._run_once()
         ri, ci = N.index_array(rows), N.index_array(cols)
