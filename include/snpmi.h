@@ -352,6 +352,49 @@ int snpmi_dev_repack(const uint8_t* src, uint64_t src_pitch, uint64_t n_src_iid,
 uint64_t snpmi_grm_tile_bytes(uint64_t n_iid, int dtype);
 int snpmi_dev_syrk_packed(const uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_t n_sid,
                           const void* lut, int dtype, void* K_tiles, int accumulate);
+/* Rect GRM: K[rows, cols] = Z[rows] Z[cols]^T computed directly, without the whole K -- the
+ * test x train kernel of SnpKernel(snps, std)[test_idx, train_idx].read(), which the reference
+ * slices out of the N x N K (kernelreader/snpkernel.py:84-88, "could be done with less memory by
+ * working in blocks").  The result is held as ceil(n_rows/256) x ceil(n_cols/256) dense row-major
+ * 256x256 blocks, block (bi, bj) at slot bj * ceil(n_rows/256) + bi (snpmi_grm_rect_bytes).
+ * Limits (SNPMI_E_ARG before any launch): < 65536 blocks per side, < 2^29 blocks, each operand's
+ * pitch % 64 == 0 and covering round_up(n, 256) iids.
+ * snpmi_dev_syrk_rect: one launch over two packed device operands (same SNP rows, same LUT
+ * [n_sid][4] of dtype); pairs (host, n_pairs x (r, c), may be NULL): positions that are diagonal
+ * elements of K, which in f32 get the exact f64 diagonal as the whole-K path's do
+ * (snpmi_rect_diag_pairs builds the list from two index lists, NULL = identity; it needs no device).
+ * snpmi_dev_rect_extract: blocks -> K_out[n_rows][n_cols] (order_c 0/1, times scale; host or device). */
+uint64_t snpmi_grm_rect_bytes(uint64_t n_rows, uint64_t n_cols, int dtype);
+int snpmi_rect_diag_pairs(const uint64_t* row_idx, uint64_t n_rows, const uint64_t* col_idx, uint64_t n_cols,
+                          uint32_t* pairs, uint64_t cap, uint64_t* count);
+int snpmi_dev_syrk_rect(const uint8_t* packed_a, uint64_t pitch_a, uint64_t n_a, const uint8_t* packed_b,
+                        uint64_t pitch_b, uint64_t n_b, uint64_t n_sid, const void* lut, int dtype, void* blocks,
+                        int accumulate, const uint32_t* pairs, uint64_t n_pairs);
+int snpmi_dev_rect_extract(const void* blocks, uint64_t n_rows, uint64_t n_cols, int dtype, int order_c, double scale,
+                           void* K_out);
+/* Rect session (beside snpmi_grm_begin / add / end): begin(n_rows, n_cols, dtype), any number of
+ * adds, end(scale, order_c, K_out; host or device, NULL = abort).  Every add standardizes with
+ * stats over ALL n_iid (add_bed: all n_out_iid selected) iids of the reader -- what
+ * SnpKernel(reader, std)[rows, cols] means -- and then takes rows row_idx / cols col_idx of them
+ * (host arrays, unsorted and repeated entries allowed, an entry >= n is SNPMI_E_INDEX; NULL = all
+ * iids in order, read in place without a repack).  add_packed: device codes as
+ * snpmi_grm_add_packed_*; add_bed: arguments as snpmi_grm_add_bed_*, the same SNP chunks. */
+int snpmi_grm_rect_begin(uint64_t n_rows, uint64_t n_cols, int dtype);
+int snpmi_grm_rect_add_packed_f32(const uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_t n_sid, int count_a1,
+                                  int std_kind, double a, double b, int use_stats, float* stats,
+                                  const uint64_t* row_idx, const uint64_t* col_idx);
+int snpmi_grm_rect_add_packed_f64(const uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_t n_sid, int count_a1,
+                                  int std_kind, double a, double b, int use_stats, double* stats,
+                                  const uint64_t* row_idx, const uint64_t* col_idx);
+int snpmi_grm_rect_add_bed_f32(const char* path, uint64_t n_iid, uint64_t n_sid, int count_a1, const uint64_t* iid_idx,
+                               uint64_t n_out_iid, const uint64_t* sid_idx, uint64_t n_out_sid, int std_kind, double a,
+                               double b, int use_stats, float* stats, int num_threads, const uint64_t* row_idx,
+                               const uint64_t* col_idx);
+int snpmi_grm_rect_add_bed_f64(const char* path, uint64_t n_iid, uint64_t n_sid, int count_a1, const uint64_t* iid_idx,
+                               uint64_t n_out_iid, const uint64_t* sid_idx, uint64_t n_out_sid, int std_kind, double a,
+                               double b, int use_stats, double* stats, int num_threads, const uint64_t* row_idx,
+                               const uint64_t* col_idx);
+int snpmi_grm_rect_end(double scale, int order_c, void* K_out);
 /* cfg5 mode (K too large to replicate): the upper triangle of the n x n K as 256x256
  * blocks, grouped into S x S-block supertiles (S = 16 once there are >= 4 supertiles per part,
  * else the largest power of two that gives as many) dealt round-robin in triangular supertile

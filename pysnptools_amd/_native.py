@@ -117,6 +117,18 @@ _SIGS = {
     "snpmi_dev_encode": [_vp, _i32, _i32, _u64, _u64, _u64, _i32, _vp, _u64, ctypes.POINTER(ctypes.c_uint64)],
     "snpmi_dev_repack": [_vp, _u64, _u64, _vp, _u64, _u64, _vp, _u64],
     "snpmi_dev_syrk_packed": [_vp, _u64, _u64, _u64, _vp, _i32, _vp, _i32],
+    "snpmi_grm_rect_bytes": [_u64, _u64, _i32],
+    "snpmi_rect_diag_pairs": [_vp, _u64, _vp, _u64, _vp, _u64, _u64p],
+    "snpmi_dev_syrk_rect": [_vp, _u64, _u64, _vp, _u64, _u64, _u64, _vp, _i32, _vp, _i32, _vp, _u64],
+    "snpmi_dev_rect_extract": [_vp, _u64, _u64, _i32, _i32, _f64, _vp],
+    "snpmi_grm_rect_begin": [_u64, _u64, _i32],
+    "snpmi_grm_rect_add_packed_f32": [_vp, _u64, _u64, _u64, _i32, _i32, _f64, _f64, _i32, _vp, _vp, _vp],
+    "snpmi_grm_rect_add_packed_f64": [_vp, _u64, _u64, _u64, _i32, _i32, _f64, _f64, _i32, _vp, _vp, _vp],
+    "snpmi_grm_rect_add_bed_f32": [_cp, _u64, _u64, _i32, _vp, _u64, _vp, _u64, _i32, _f64, _f64, _i32, _vp, _i32,
+                                   _vp, _vp],
+    "snpmi_grm_rect_add_bed_f64": [_cp, _u64, _u64, _i32, _vp, _u64, _vp, _u64, _i32, _f64, _f64, _i32, _vp, _i32,
+                                   _vp, _vp],
+    "snpmi_grm_rect_end": [_f64, _i32, _vp],
     "snpmi_grm_part_blocks": [_u64, _i32, _i32],
     "snpmi_grm_part_coords": [_u64, _i32, _i32, _u64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)],
     "snpmi_grm_part_coords_all": [_u64, _i32, _i32, _vp],
@@ -149,7 +161,8 @@ _SIGS = {
     "snpmi_last_error": [],
 }
 _RESTYPES = {"snpmi_last_error": ctypes.c_char_p, "snpmi_packed_pitch": ctypes.c_uint64,
-             "snpmi_grm_tile_bytes": ctypes.c_uint64, "snpmi_grm_part_blocks": ctypes.c_uint64}
+             "snpmi_grm_tile_bytes": ctypes.c_uint64, "snpmi_grm_part_blocks": ctypes.c_uint64,
+             "snpmi_grm_rect_bytes": ctypes.c_uint64}
 
 _lib = None
 _load_error = None

@@ -1556,6 +1556,267 @@ static void grm_add_bed_reduce_impl(const char* path, uint64_t n_iid, uint64_t n
     }
     session_sum_planned<T>(d, collective, rt, parts, nullptr);  // no SNP on this rank: zeros join the sum
 }
+
+// ---------------------------------------------------------------------- rect GRM: K[rows, cols] directly
+// K[rows, cols] = Z[rows] Z[cols]^T without the whole K (the reference slices the N x N K,
+// kernelreader/snpkernel.py:84-88).  Each SNP chunk is repacked to the rows and to the cols
+// (launch_repack; an identity side is read in place) and the two-operand kernels write the
+// ceil(n_r / 256) x ceil(n_c / 256) dense blocks.  Stats and the LUT come from all the reader's iids.
+
+// positions (r, c) with rows[r] == cols[c]: the diagonal elements of K inside the rectangle
+// (idx == nullptr: the identity list).  Repeats give every combination.
+static void rect_diag_pairs(const uint64_t* ri, uint64_t nr, const uint64_t* ci, uint64_t nc,
+                            std::vector<uint32_t>& pairs) {
+    pairs.clear();
+    if (nr == 0 || nc == 0) return;
+    SNPMI_REQUIRE(nr < (1ull << 32) && nc < (1ull << 32), SNPMI_E_ARG, "rect GRM: too many rows / cols");
+    if (!ci) {
+        for (uint64_t r = 0; r < nr; r++) {
+            const uint64_t i = ri ? ri[r] : r;
+            if (i < nc) pairs.push_back((uint32_t)r), pairs.push_back((uint32_t)i);
+        }
+        return;
+    }
+    std::vector<uint32_t> order(nc);
+    for (uint64_t c = 0; c < nc; c++) order[c] = (uint32_t)c;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return ci[x] < ci[y]; });
+    for (uint64_t r = 0; r < nr; r++) {
+        const uint64_t i = ri ? ri[r] : r;
+        auto it = std::lower_bound(order.begin(), order.end(), i, [&](uint32_t x, uint64_t v) { return ci[x] < v; });
+        for (; it != order.end() && ci[*it] == i; ++it) pairs.push_back((uint32_t)r), pairs.push_back(*it);
+    }
+}
+
+// one side (rows or cols) of a rect call: its index list on the device and the repack plan
+struct RectSide {
+    uint64_t n = 0, n_src = 0, pitch = 0;
+    bool identity = true;
+    uint64_t* idx_dev = nullptr;
+    RepackPlan plan;
+    Device::Slot dst = Device::S_RECT_A;
+};
+
+static RectSide rect_side(Device& d, const uint64_t* idx, uint64_t n_sel, uint64_t n_src, int which) {
+    RectSide s;
+    SNPMI_REQUIRE(idx || n_sel == n_src || n_sel == 0, SNPMI_E_ARG, "rect GRM: a NULL index list means all iids");
+    for (uint64_t k = 0; idx && k < n_sel; k++) SNPMI_REQUIRE(idx[k] < n_src, SNPMI_E_INDEX, "iid index out of range");
+    s.n = n_sel;
+    s.n_src = n_src;
+    s.pitch = packed_pitch(n_sel);
+    s.identity = n_sel == n_src && is_identity(idx, n_sel, n_src);
+    s.dst = which ? Device::S_RECT_B : Device::S_RECT_A;
+    if (!s.identity && n_sel) {
+        s.idx_dev = (uint64_t*)d.get(which ? Device::S_RECT_IDX_B : Device::S_RECT_IDX_A, n_sel * 8);
+        SNPMI_HIP(hipMemcpyAsync(s.idx_dev, idx, n_sel * 8, hipMemcpyHostToDevice, d.stream));
+        uint32_t* plan = (uint32_t*)d.get(which ? Device::S_RECT_PLAN_B : Device::S_RECT_PLAN_A,
+                                          repack_plan_entries(n_sel) * 4);
+        uint32_t* win = (uint32_t*)d.get(which ? Device::S_RECT_WIN_B : Device::S_RECT_WIN_A,
+                                         repack_win_entries(n_sel) * 4);
+        s.plan = launch_repack_plan(s.idx_dev, n_sel, n_src, plan, win, d.stream);
+        SNPMI_HIP(hipStreamSynchronize(d.stream));  // idx is the caller's host memory
+    }
+    return s;
+}
+
+// the side's operand for one SNP chunk: the chunk itself (identity) or its repack
+static const uint8_t* rect_operand(Device& d, const RectSide& s, const uint8_t* packed, uint64_t pitch, uint64_t cnt,
+                                   uint64_t* pitch_out) {
+    if (s.identity) {
+        *pitch_out = pitch;
+        return packed;
+    }
+    uint8_t* dst = (uint8_t*)d.get(s.dst, cnt * s.pitch);
+    launch_repack(packed, pitch, s.n_src, s.idx_dev, s.plan, s.n, cnt, dst, s.pitch, d.stream);
+    *pitch_out = s.pitch;
+    return dst;
+}
+
+// diagonal pairs on the device: npairs x (r, c) u32, then npairs f64 of saved values
+struct RectPairs {
+    const uint32_t* pairs = nullptr;
+    double* saved = nullptr;
+    uint64_t n = 0;
+};
+static RectPairs rect_pairs_upload(Device& d, const uint32_t* host_pairs, uint64_t npairs) {
+    RectPairs p;
+    if (npairs == 0) return p;
+    uint8_t* base = (uint8_t*)d.get(Device::S_RECT_PAIRS, npairs * 16);
+    SNPMI_HIP(hipMemcpyAsync(base, host_pairs, npairs * 8, hipMemcpyHostToDevice, d.stream));
+    SNPMI_HIP(hipStreamSynchronize(d.stream));
+    p.pairs = (const uint32_t*)base;
+    p.saved = (double*)(base + npairs * 8);
+    p.n = npairs;
+    return p;
+}
+
+// blocks (+)= Za Zb^T of one SNP block: f64 on the CRT path in crt_max_snps() steps (the f64 MFMA
+// kernel gated on its non-finite flag), f32 on the fp16x2 / bf16x3 chain with the exact diagonal
+// of the matched positions (hook "diag"), as syrk_packed_auto does for the whole K
+static void syrk_rect_auto(Device& d, const uint8_t* Pa, uint64_t pitch_a, uint64_t na, const uint8_t* Pb,
+                           uint64_t pitch_b, uint64_t nb, uint64_t m, const void* lut, int dt, void* blocks,
+                           int accumulate, const RectPairs& dp) {
+    const uint64_t g = rect_blocks(na, pitch_a, nb, pitch_b);
+    if (g == 0) return;
+    if (m == 0) {
+        if (!accumulate) SNPMI_HIP(hipMemsetAsync(blocks, 0, g * 65536 * dtype_size(dt), d.stream));
+        return;
+    }
+    if (dt == SNPMI_DT_F64) {
+        const double* L = (const double*)lut;
+        const bool crt = syrk_f64_path() == F64Path::CRT;
+        const uint64_t step = crt_max_snps();
+        const uint64_t res_bytes = std::min<uint64_t>(g * (uint64_t)crt_moduli() * 65536, 4ull << 30);
+        uint8_t* res = crt ? (uint8_t*)d.get(Device::S_ZBLK, res_bytes) : nullptr;
+        void* ws = crt ? d.get(Device::S_LUT3, crt_rect_lut_bytes(std::min(m, step), na, nb)) : nullptr;
+        unsigned long long* rec = crt ? crt_record(d) : nullptr;
+        for (uint64_t s0 = 0; s0 < m; s0 += step) {
+            const uint64_t cnt = std::min(step, m - s0);
+            const int acc = accumulate || s0 > 0;
+            if (crt)
+                launch_syrk_rect_crt(Pa + s0 * pitch_a, pitch_a, na, Pb + s0 * pitch_b, pitch_b, nb, cnt, L + 4 * s0,
+                                     (double*)blocks, acc, ws, res, res_bytes, rec, d.stream);
+            launch_syrk_rect_f64(Pa + s0 * pitch_a, pitch_a, na, Pb + s0 * pitch_b, pitch_b, nb, cnt, L + 4 * s0,
+                                 (double*)blocks, acc, d.stream, crt ? (const int*)ws + 1 : nullptr);
+        }
+        return;
+    }
+    H2Lut h2;
+    const bool h = syrk_f32_path() == F32Path::H2;
+    const uint32_t* l3 = lut_bf3(d, (const float*)lut, m, h ? &h2 : nullptr);
+    const bool exact = g_diag_exact && dp.n > 0;
+    if (exact) launch_rect_diag_save((const float*)blocks, ceil_div(na, 256), dp.pairs, dp.n, accumulate, dp.saved, d.stream);
+    launch_syrk_rect_f32(Pa, pitch_a, na, Pb, pitch_b, nb, m, l3, h ? &h2 : nullptr, (float*)blocks, accumulate, d.stream);
+    if (exact) {
+        double* sq = (double*)d.get(Device::S_DIAG, diag_scratch_bytes(na, m));
+        SNPMI_HIP(hipMemsetAsync(sq, 0, round_up(na, 16) * sizeof(double), d.stream));
+        launch_diag_sq(Pa, pitch_a, na, m, (const float*)lut, sq, d.stream);
+        launch_rect_diag_patch((float*)blocks, ceil_div(na, 256), dp.pairs, dp.n, dp.saved, sq, d.stream);
+    }
+}
+
+static uint64_t rect_bytes(uint64_t nr, uint64_t nc, int dt) {
+    return ceil_div(nr, 256) * ceil_div(nc, 256) * 65536 * dtype_size(dt);
+}
+
+// blocks -> K_out[n_r][n_c] (host or device), modelled on grm_finish: one launch for a device
+// K_out, <= 1 GiB staging blocks of the slow axis for a host K_out
+template <typename T>
+static void rect_extract(Device& d, const T* blocks, uint64_t nr, uint64_t nc, int order_c, double scale, T* K_out) {
+    if (nr * nc == 0) return;
+    const uint64_t outer = order_c ? nr : nc, inner = order_c ? nc : nr, nba = ceil_div(nr, 256);
+    const bool dev = is_device_ptr(d, K_out);
+    const uint64_t per = dev ? outer : std::max<uint64_t>(1, std::min<uint64_t>(outer, (1ull << 30) / (inner * sizeof(T))));
+    for (uint64_t o0 = 0; o0 < outer; o0 += per) {
+        const uint64_t no = std::min(per, outer - o0);
+        T* dk = dev ? K_out : (T*)d.get(Device::S_K, no * inner * sizeof(T));
+        launch_rect_extract(blocks, DT<T>::v, nba, inner, o0, no, order_c, scale, dk, d.stream);
+        if (!dev)
+            d2h_rows(d, K_out + o0 * inner, inner * sizeof(T), dk, inner * sizeof(T), inner * sizeof(T), no,
+                     resolve_threads(0));
+    }
+    SNPMI_HIP(hipStreamSynchronize(d.stream));
+}
+
+struct RectSession {
+    bool active = false;
+    bool wrote = false;
+    uint64_t nr = 0, nc = 0;
+    int dtype = SNPMI_DT_F32;
+};
+static RectSession g_rect;
+
+static void* rect_session_blocks(Device& d) { return d.get(Device::S_RECT, rect_bytes(g_rect.nr, g_rect.nc, g_rect.dtype)); }
+
+template <typename T>
+static void rect_check_session(uint64_t n, const uint64_t* row_idx, const uint64_t* col_idx) {
+    SNPMI_REQUIRE(g_rect.active, SNPMI_E_ARG, "no rect GRM session (call snpmi_grm_rect_begin)");
+    SNPMI_REQUIRE(g_rect.dtype == DT<T>::v, SNPMI_E_ARG, "dtype differs from snpmi_grm_rect_begin");
+    SNPMI_REQUIRE(row_idx || g_rect.nr == n || g_rect.nr == 0, SNPMI_E_ARG, "row count differs from snpmi_grm_rect_begin");
+    SNPMI_REQUIRE(col_idx || g_rect.nc == n || g_rect.nc == 0, SNPMI_E_ARG, "col count differs from snpmi_grm_rect_begin");
+}
+
+// the sides, the diagonal pairs and the per-chunk multiply of one add call
+struct RectAdd {
+    RectSide rows, cols;
+    RectPairs dp;
+    void* blocks = nullptr;
+};
+template <typename T>
+static RectAdd rect_add_begin(Device& d, uint64_t n, const uint64_t* row_idx, const uint64_t* col_idx) {
+    RectAdd a;
+    a.rows = rect_side(d, row_idx, g_rect.nr, n, 0);
+    a.cols = rect_side(d, col_idx, g_rect.nc, n, 1);
+    (void)rect_blocks(g_rect.nr, a.rows.pitch, g_rect.nc, a.cols.pitch);
+    if (DT<T>::v == SNPMI_DT_F32 && g_diag_exact) {
+        std::vector<uint32_t> pairs;
+        rect_diag_pairs(row_idx, g_rect.nr, col_idx, g_rect.nc, pairs);
+        a.dp = rect_pairs_upload(d, pairs.data(), pairs.size() / 2);
+    }
+    a.blocks = rect_session_blocks(d);
+    return a;
+}
+template <typename T>
+static void rect_add_chunk(Device& d, const RectAdd& a, const uint8_t* packed, uint64_t pitch, uint64_t cnt,
+                           const T* lut) {
+    if (g_rect.nr == 0 || g_rect.nc == 0 || cnt == 0) return;
+    uint64_t pa = 0, pb = 0;
+    const uint8_t* A = rect_operand(d, a.rows, packed, pitch, cnt, &pa);
+    const uint8_t* B = rect_operand(d, a.cols, packed, pitch, cnt, &pb);
+    syrk_rect_auto(d, A, pa, g_rect.nr, B, pb, g_rect.nc, cnt, lut, DT<T>::v, a.blocks, g_rect.wrote ? 1 : 0, a.dp);
+    g_rect.wrote = true;
+}
+
+template <typename T>
+static void rect_add_packed_impl(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, int count_a1,
+                                 int std_kind, double a, double b, int use_stats, T* stats, const uint64_t* row_idx,
+                                 const uint64_t* col_idx) {
+    std::lock_guard<std::recursive_mutex> lk(g_call_mutex);
+    rect_check_session<T>(n, row_idx, col_idx);
+    SNPMI_REQUIRE(pitch % 64 == 0 && pitch >= ceil_div(n, 4), SNPMI_E_ARG, "pitch must be snpmi_packed_pitch");
+    SNPMI_REQUIRE(std_kind >= SNPMI_STD_NONE && std_kind <= SNPMI_STD_BETA, SNPMI_E_ARG, "bad standardizer kind");
+    SNPMI_REQUIRE(stats != nullptr || std_kind == SNPMI_STD_NONE || m == 0, SNPMI_E_ARG, "stats is NULL");
+    Device& d = device();
+    const RectAdd ra = rect_add_begin<T>(d, n, row_idx, col_idx);
+    if (m == 0 || n == 0) return;
+    SNPMI_REQUIRE(packed != nullptr && is_device_ptr(d, packed), SNPMI_E_ARG,
+                  "packed must be device memory of the current device");
+    const bool host_stats = stats && std_kind != SNPMI_STD_NONE && !is_device_ptr(d, stats);
+    // the chunks of snpmi_grm_add_packed_*: the same launch boundaries as the whole-K session
+    const uint64_t nchunk = ceil_div(m, 1ull << 16);
+    const uint64_t step = std::min<uint64_t>(1ull << 16, round_up(ceil_div(m, nchunk), 256));
+    for (uint64_t s0 = 0; s0 < m; s0 += step) {
+        const uint64_t cnt = std::min(step, m - s0);
+        const uint8_t* src = packed + s0 * pitch;
+        T* lut = (T*)d.get(Device::S_LUT, cnt * 4 * sizeof(T));
+        T* st = (stats && !host_stats) ? stats + 2 * s0 : (T*)d.get(Device::S_STATS, cnt * 2 * sizeof(T));
+        if (host_stats && use_stats)
+            SNPMI_HIP(hipMemcpyAsync(st, stats + 2 * s0, cnt * 2 * sizeof(T), hipMemcpyHostToDevice, d.stream));
+        launch_snp_stats(src, pitch, n, cnt, count_a1, std_kind, a, b, use_stats, DT<T>::v, st, lut, d.stream);
+        rect_add_chunk<T>(d, ra, src, pitch, cnt, lut);
+        if (host_stats && !use_stats) {
+            SNPMI_HIP(hipMemcpyAsync(stats + 2 * s0, st, cnt * 2 * sizeof(T), hipMemcpyDeviceToHost, d.stream));
+            SNPMI_HIP(hipStreamSynchronize(d.stream));  // S_STATS is reused by the next chunk
+        }
+    }
+    SNPMI_HIP(hipStreamSynchronize(d.stream));
+}
+
+template <typename T>
+static void rect_add_bed_impl(const char* path, uint64_t n_iid, uint64_t n_sid, int count_a1, const uint64_t* iid_idx,
+                              uint64_t n_out_iid, const uint64_t* sid_idx, uint64_t n_out_sid, int std_kind, double a,
+                              double b, int use_stats, T* stats, int num_threads, const uint64_t* row_idx,
+                              const uint64_t* col_idx) {
+    std::lock_guard<std::recursive_mutex> lk(g_call_mutex);
+    const uint64_t n = iid_idx ? n_out_iid : n_iid;
+    rect_check_session<T>(n, row_idx, col_idx);
+    Device& d = device();
+    const RectAdd ra = rect_add_begin<T>(d, n, row_idx, col_idx);
+    grm_stream_bed<T>(d, false, path, n_iid, n_sid, count_a1, iid_idx, n_out_iid, sid_idx, n_out_sid, std_kind, a, b,
+                      use_stats, stats, num_threads,
+                      [&](const uint8_t* packed, uint64_t pitch, uint64_t nn, uint64_t cnt, const T* lut, bool) {
+                          rect_add_chunk<T>(d, ra, packed, pitch, cnt, lut);
+                      });
+}
 }  // namespace snpmi
 
 // ====================================================================== exported C ABI
@@ -1912,6 +2173,113 @@ int snpmi_grm_end(int diag_k_to_n, double* factor, void* K_out) {
             grm_finish(d, (const float*)t, g_session.n, diag_k_to_n, factor, (float*)K_out);
         else
             grm_finish(d, (const double*)t, g_session.n, diag_k_to_n, factor, (double*)K_out);
+    });
+}
+
+// ---- rect GRM (K[rows, cols] directly)
+uint64_t snpmi_grm_rect_bytes(uint64_t n_rows, uint64_t n_cols, int dtype) { return rect_bytes(n_rows, n_cols, dtype); }
+
+int snpmi_rect_diag_pairs(const uint64_t* row_idx, uint64_t n_rows, const uint64_t* col_idx, uint64_t n_cols,
+                          uint32_t* pairs, uint64_t cap, uint64_t* count) {
+    return guarded([&] {
+        SNPMI_REQUIRE(count != nullptr, SNPMI_E_ARG, "count is NULL");
+        std::vector<uint32_t> v;
+        rect_diag_pairs(row_idx, n_rows, col_idx, n_cols, v);
+        *count = v.size() / 2;
+        if (pairs) std::memcpy(pairs, v.data(), std::min<uint64_t>(cap, v.size() / 2) * 8);
+    });
+}
+
+int snpmi_dev_syrk_rect(const uint8_t* packed_a, uint64_t pitch_a, uint64_t n_a, const uint8_t* packed_b,
+                        uint64_t pitch_b, uint64_t n_b, uint64_t n_sid, const void* lut, int dtype, void* blocks,
+                        int accumulate, const uint32_t* pairs, uint64_t n_pairs) {
+    return guarded([&] {
+        std::lock_guard<std::recursive_mutex> lk(g_call_mutex);  // shared scratch slots
+        SNPMI_REQUIRE(dtype == SNPMI_DT_F32 || dtype == SNPMI_DT_F64, SNPMI_E_ARG, "GRM dtype must be f32/f64");
+        Device& d = device();
+        for (uint64_t k = 0; k < n_pairs; k++)
+            SNPMI_REQUIRE(pairs && pairs[2 * k] < n_a && pairs[2 * k + 1] < n_b, SNPMI_E_INDEX, "diagonal pair out of range");
+        (void)rect_blocks(n_a, pitch_a, n_b, pitch_b);
+        const RectPairs dp = dtype == SNPMI_DT_F32 ? rect_pairs_upload(d, pairs, n_pairs) : RectPairs();
+        syrk_rect_auto(d, packed_a, pitch_a, n_a, packed_b, pitch_b, n_b, n_sid, lut, dtype, blocks, accumulate, dp);
+    });
+}
+
+int snpmi_dev_rect_extract(const void* blocks, uint64_t n_rows, uint64_t n_cols, int dtype, int order_c, double scale,
+                           void* K_out) {
+    return guarded([&] {
+        std::lock_guard<std::recursive_mutex> lk(g_call_mutex);  // shared scratch slots
+        SNPMI_REQUIRE(dtype == SNPMI_DT_F32 || dtype == SNPMI_DT_F64, SNPMI_E_ARG, "GRM dtype must be f32/f64");
+        SNPMI_REQUIRE(K_out != nullptr || n_rows * n_cols == 0, SNPMI_E_ARG, "K_out is NULL");
+        Device& d = device();
+        if (dtype == SNPMI_DT_F32) rect_extract(d, (const float*)blocks, n_rows, n_cols, order_c, scale, (float*)K_out);
+        else rect_extract(d, (const double*)blocks, n_rows, n_cols, order_c, scale, (double*)K_out);
+    });
+}
+
+int snpmi_grm_rect_begin(uint64_t n_rows, uint64_t n_cols, int dtype) {
+    return guarded([&] {
+        std::lock_guard<std::recursive_mutex> lk(g_call_mutex);
+        SNPMI_REQUIRE(dtype == SNPMI_DT_F32 || dtype == SNPMI_DT_F64, SNPMI_E_ARG, "GRM dtype must be f32 or f64");
+        SNPMI_REQUIRE(ceil_div(n_rows, 256) < 65536 && ceil_div(n_cols, 256) < 65536 &&
+                          ceil_div(n_rows, 256) * ceil_div(n_cols, 256) < (1ull << 29),
+                      SNPMI_E_ARG, "rect GRM: too many 256-iid blocks");
+        Device& d = device();
+        g_rect = RectSession{true, false, n_rows, n_cols, dtype};
+        (void)rect_session_blocks(d);
+    });
+}
+
+int snpmi_grm_rect_add_packed_f32(const uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_t n_sid, int count_a1,
+                                  int std_kind, double a, double b, int use_stats, float* stats,
+                                  const uint64_t* row_idx, const uint64_t* col_idx) {
+    return guarded([&] {
+        rect_add_packed_impl<float>(packed, pitch, n_iid, n_sid, count_a1, std_kind, a, b, use_stats, stats, row_idx, col_idx);
+    });
+}
+int snpmi_grm_rect_add_packed_f64(const uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_t n_sid, int count_a1,
+                                  int std_kind, double a, double b, int use_stats, double* stats,
+                                  const uint64_t* row_idx, const uint64_t* col_idx) {
+    return guarded([&] {
+        rect_add_packed_impl<double>(packed, pitch, n_iid, n_sid, count_a1, std_kind, a, b, use_stats, stats, row_idx, col_idx);
+    });
+}
+int snpmi_grm_rect_add_bed_f32(const char* path, uint64_t n_iid, uint64_t n_sid, int count_a1, const uint64_t* iid_idx,
+                               uint64_t n_out_iid, const uint64_t* sid_idx, uint64_t n_out_sid, int std_kind, double a,
+                               double b, int use_stats, float* stats, int num_threads, const uint64_t* row_idx,
+                               const uint64_t* col_idx) {
+    return guarded([&] {
+        rect_add_bed_impl<float>(path, n_iid, n_sid, count_a1, iid_idx, n_out_iid, sid_idx, n_out_sid, std_kind, a, b,
+                                 use_stats, stats, num_threads, row_idx, col_idx);
+    });
+}
+int snpmi_grm_rect_add_bed_f64(const char* path, uint64_t n_iid, uint64_t n_sid, int count_a1, const uint64_t* iid_idx,
+                               uint64_t n_out_iid, const uint64_t* sid_idx, uint64_t n_out_sid, int std_kind, double a,
+                               double b, int use_stats, double* stats, int num_threads, const uint64_t* row_idx,
+                               const uint64_t* col_idx) {
+    return guarded([&] {
+        rect_add_bed_impl<double>(path, n_iid, n_sid, count_a1, iid_idx, n_out_iid, sid_idx, n_out_sid, std_kind, a, b,
+                                  use_stats, stats, num_threads, row_idx, col_idx);
+    });
+}
+
+int snpmi_grm_rect_end(double scale, int order_c, void* K_out) {
+    return guarded([&] {
+        std::lock_guard<std::recursive_mutex> lk(g_call_mutex);
+        SNPMI_REQUIRE(g_rect.active, SNPMI_E_ARG, "no rect GRM session (call snpmi_grm_rect_begin)");
+        Device& d = device();
+        g_rect.active = false;
+        if (!K_out || g_rect.nr * g_rect.nc == 0) {  // an aborted session, or an empty result
+            SNPMI_HIP(hipStreamSynchronize(d.stream));
+            return;
+        }
+        void* t = rect_session_blocks(d);
+        if (!g_rect.wrote)
+            SNPMI_HIP(hipMemsetAsync(t, 0, rect_bytes(g_rect.nr, g_rect.nc, g_rect.dtype), d.stream));
+        if (g_rect.dtype == SNPMI_DT_F32)
+            rect_extract(d, (const float*)t, g_rect.nr, g_rect.nc, order_c, scale, (float*)K_out);
+        else
+            rect_extract(d, (const double*)t, g_rect.nr, g_rect.nc, order_c, scale, (double*)K_out);
     });
 }
 

@@ -90,7 +90,10 @@ struct Device {
     // grow-only scratch slots
     enum Slot { S_PACKED, S_PACKED2, S_IDX, S_IDX2, S_LUT, S_STATS, S_OUT, S_TILES, S_K, S_DENSE,
                 S_DENSE2, S_RED, S_SESSION, S_PACKED_B, S_ZBLK, S_IDX32, S_LUT3, S_H2, S_OUT_B, S_STATS_B,
-                S_WIN, S_DPACK, S_DLUT, S_CRTREC, S_SEG, S_STDFLAG, S_DIAG, S_NUM };
+                S_WIN, S_DPACK, S_DLUT, S_CRTREC, S_SEG, S_STDFLAG, S_DIAG,
+                // rect GRM session: blocks, the two repacked operands, per side index / plan / window, diagonal pairs
+                S_RECT, S_RECT_A, S_RECT_B, S_RECT_IDX_A, S_RECT_IDX_B, S_RECT_PLAN_A, S_RECT_PLAN_B, S_RECT_WIN_A,
+                S_RECT_WIN_B, S_RECT_PAIRS, S_NUM };
     void* buf[S_NUM] = {};
     // chunk pipeline events (slot = chunk parity), all on-device ordering, no host spin:
     hipEvent_t staged[2] = {};    // copy stream: H2D of pinned slot done (host may refill it)
@@ -258,6 +261,47 @@ struct GrmDest {
     uint64_t blocks;       // 256-iid blocks: the whole upper triangle's, or the part's
 };
 uint64_t grm_part_blocks(uint64_t n, int rank, int world);
+// Two-operand ("rect") GRM, K[rows, cols] = Za Zb^T: the SYRK kernels' RECT instantiations read
+// block row bi's A panel from their own (P, pitch) and block column bj's B panel from this second
+// operand (same SNP rows, same LUT), run every block of the ceil(n_a / 256) x ceil(n_b / 256) grid
+// and write block (bi, bj) as a dense row-major 256 x 256 block at slot bj * nba + bi (bi fastest:
+// the blocks in flight share a B panel).  The RECT = false instantiations carry an empty argument
+// and are the kernels as they were.
+template <bool RECT>
+struct RectArg {};
+template <>
+struct RectArg<true> {
+    const uint8_t* P;   // second operand's codes [m][pitch]
+    uint64_t pitch;
+    uint32_t nba;       // block rows of the rectangle
+    const double* lgp;  // CRT path: per-panel log2 bounds of the second operand (k_crt_panels)
+};
+// limits (SNPMI_E_ARG): < 65536 blocks per side, < 2^29 blocks, both pitches % 64 == 0 and covering
+// round_up(n, 256) iids; returns the block count
+uint64_t rect_blocks(uint64_t n_a, uint64_t pitch_a, uint64_t n_b, uint64_t pitch_b);
+struct H2Lut;
+void launch_syrk_rect_f32(const uint8_t* Pa, uint64_t pitch_a, uint64_t n_a, const uint8_t* Pb, uint64_t pitch_b,
+                          uint64_t n_b, uint64_t m, const uint32_t* lut3, const H2Lut* h2, float* blocks,
+                          int accumulate, hipStream_t st);
+void launch_syrk_rect_f64(const uint8_t* Pa, uint64_t pitch_a, uint64_t n_a, const uint8_t* Pb, uint64_t pitch_b,
+                          uint64_t n_b, uint64_t m, const double* lut, double* blocks, int accumulate, hipStream_t st,
+                          const int* gate = nullptr);
+// the CRT form: ws_lut = crt_rect_lut_bytes(m, n_a, n_b); one bound table per operand, block (bi, bj)
+// runs the moduli with P_R > 2 sqrt(M_bi(A) M_bj(B))
+uint64_t crt_rect_lut_bytes(uint64_t m, uint64_t n_a, uint64_t n_b);
+void launch_syrk_rect_crt(const uint8_t* Pa, uint64_t pitch_a, uint64_t n_a, const uint8_t* Pb, uint64_t pitch_b,
+                          uint64_t n_b, uint64_t m, const double* lut, double* blocks, int accumulate, void* ws_lut,
+                          uint8_t* res, uint64_t res_bytes, unsigned long long* rec, hipStream_t st);
+// rect blocks -> the outer range [o0, o0 + no) of K_out's slow axis (rows if order_c, else columns;
+// `inner` = the fast axis' length), contiguous, times scale (rect.hip)
+void launch_rect_extract(const void* blocks, int dtype, uint64_t nba, uint64_t inner, uint64_t o0, uint64_t no,
+                         int order_c, double scale, void* out, hipStream_t st);
+// exact f32 diagonal of a rect launch: pairs (r, c) with rows[r] == cols[c] (u32 x 2 each, device);
+// save keeps their current values as f64 (0 unless accumulating), patch writes saved + sq[r] back
+void launch_rect_diag_save(const float* blocks, uint64_t nba, const uint32_t* pairs, uint64_t npairs, int accumulate,
+                           double* saved, hipStream_t st);
+void launch_rect_diag_patch(float* blocks, uint64_t nba, const uint32_t* pairs, uint64_t npairs, const double* saved,
+                            const double* sq, hipStream_t st);
 // fused packed kernels on the f32 / f64 MFMA; gate (f64): run only if that device word is non-zero
 void launch_syrk_packed(const uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_t n_sid, const void* lut,
                         int dtype, const GrmDest& o, int accumulate, hipStream_t st, const int* gate = nullptr);

@@ -630,14 +630,15 @@ struct B3Regs {
     uint4 la, lb;  // plane LUT words: (lo0, hi0, lo1, hi1), (lo2, hi2, -, -)
 };
 
-template <bool LOCAL = false>
+template <bool LOCAL = false, bool RECT = false>
 __global__ __launch_bounds__(512, 1) void k_syrk_bf3(const uint8_t* __restrict__ P, uint64_t pitch, uint64_t n,
                                                      uint64_t kdim, const uint32_t* __restrict__ lut3,
                                                      float* __restrict__ tiles, int accumulate,
                                                      uint32_t part_rank = 0, uint32_t part_world = 1,
                                                      uint64_t kslice = 0, uint64_t slice_elems = 0,
                                                      const uint32_t* __restrict__ gate = nullptr, SegCtx seg = SegCtx(),
-                                                     uint64_t wg0 = 0, const uint32_t* __restrict__ part_tab = nullptr) {
+                                                     uint64_t wg0 = 0, const uint32_t* __restrict__ part_tab = nullptr,
+                                                     RectArg<RECT> rb = RectArg<RECT>()) {
     __shared__ __attribute__((aligned(16))) short lds[2 * B3_STAGE];
     if (gate && *gate == 0) return;  // fallback of k_syrk_h2: runs only when its range flag is set
     if (gridDim.y > 1) {  // split-K: slice blockIdx.y covers SNPs [y*kslice, +kslice) into its own partial K
@@ -650,7 +651,10 @@ __global__ __launch_bounds__(512, 1) void k_syrk_bf3(const uint8_t* __restrict__
     // wg0: first block of a column-group launch (triangular order), as in k_syrk_h2
     const uint64_t wg = wg0 + blockIdx.x;
     uint32_t bi, bj;
-    if constexpr (LOCAL) {  // slot wg of the part's layout table (part_layout)
+    if constexpr (RECT) {  // two operands: every block of the rectangle, bi fastest inside bj
+        bi = (uint32_t)(wg % rb.nba);
+        bj = (uint32_t)(wg / rb.nba);
+    } else if constexpr (LOCAL) {  // slot wg of the part's layout table (part_layout)
         bi = part_tab[wg] & 0xffffu;
         bj = part_tab[wg] >> 16;
     } else {
@@ -668,6 +672,12 @@ __global__ __launch_bounds__(512, 1) void k_syrk_bf3(const uint8_t* __restrict__
     const int sw = (ld_ >> 2) & 1;
     // packed codes of (SNP k0 + lk, iids base + 16 ld_ ..): walked by pointer, clamped to the last
     // SNP past kdim (its values are zeroed through the LUT: lut3 is zero-padded to a multiple of BK)
+    if constexpr (RECT) {  // the B panel's loader threads read the second operand
+        if (lp) {
+            P = rb.P;
+            pitch = rb.pitch;
+        }
+    }
     const uint8_t* wp = P + (lp ? j0 : i0) / 4 + 4 * ld_ + (uint64_t)lk * pitch;
     const uint8_t* wlast = P + (lp ? j0 : i0) / 4 + 4 * ld_ + (kdim - 1) * pitch;
     const uint32_t* lp3 = lut3 + 8 * lk;
@@ -816,7 +826,7 @@ __global__ __launch_bounds__(512, 1) void k_syrk_bf3(const uint8_t* __restrict__
             if (sf.due(s + 2 < nst)) sf.flush(acc);
         }
         sf.finish(acc);
-        epilogue_pi<LOCAL>(acc, tiles, n, bi, bj, accumulate, lane, wm, wn, wg);
+        epilogue_pi<LOCAL || RECT>(acc, tiles, n, bi, bj, accumulate, lane, wm, wn, wg);
         sf.release(seg);
     }
 }
@@ -1209,14 +1219,14 @@ __global__ __launch_bounds__(512, 1) void k_syrk_h2(const uint8_t* __restrict__ 
 // x 2 planes per thread and stage, ds_write_b64 -- and issue stage s+2's code / LUT loads while the
 // MFMA waves compute stage s.  One barrier per 32-SNP stage, as in MODE 4.  Register budget of 3
 // waves per SIMD (<= 168): the MFMA waves hold each k-step's B planes and ONE A plane at a time.
-template <bool LOCAL = false>
+template <bool LOCAL = false, bool RECT = false>
 __global__ __launch_bounds__(768, 1) void k_syrk_h2s(const uint8_t* __restrict__ P, uint64_t pitch, uint64_t n,
                                                      uint64_t kdim, const uint32_t* __restrict__ lut2,
                                                      const uint32_t* __restrict__ flag, float* __restrict__ tiles,
                                                      int accumulate, uint32_t part_rank = 0, uint32_t part_world = 1,
                                                      uint64_t kslice = 0, uint64_t slice_elems = 0,
                                                      SegCtx seg = SegCtx(), const uint32_t* __restrict__ order = nullptr,
-                                                     uint64_t wg0 = 0) {
+                                                     uint64_t wg0 = 0, RectArg<RECT> rb = RectArg<RECT>()) {
     constexpr int KS = 2, SBK = KS * BK;
     constexpr int PLANE = KS * B3_PLANE, STAGE = 2 * 2 * PLANE;
     __shared__ __attribute__((aligned(16))) short lds[2 * STAGE];
@@ -1230,7 +1240,10 @@ __global__ __launch_bounds__(768, 1) void k_syrk_h2s(const uint8_t* __restrict__
     }
     const uint64_t wg = wg0 + blockIdx.x;
     uint32_t bi, bj;
-    if (LOCAL || order) {
+    if constexpr (RECT) {  // two operands: every block of the rectangle, bi fastest inside bj
+        bi = (uint32_t)(wg % rb.nba);
+        bj = (uint32_t)(wg / rb.nba);
+    } else if (LOCAL || order) {
         const uint32_t c = order[wg];
         bi = c & 0xffffu;
         bj = c >> 16;
@@ -1247,6 +1260,12 @@ __global__ __launch_bounds__(768, 1) void k_syrk_h2s(const uint8_t* __restrict__
         // loader thread lt = (panel lp, SNP rows lk + 8u of the stage (u < 4), 16-iid group ld_)
         const int lt = t - 512;
         const int lp = __builtin_amdgcn_readfirstlane(lt >> 7), lk = (lt >> 4) & 7, ld_ = lt & 15;
+        if constexpr (RECT) {  // the B panel's loader waves read the second operand
+            if (lp) {
+                P = rb.P;
+                pitch = rb.pitch;
+            }
+        }
         const uint64_t c0 = (uint64_t)(lp ? bj : bi) * BW;
         const uint8_t* wp = P + c0 / 4 + 4 * ld_ + (uint64_t)lk * pitch;
         const uint8_t* wlast = P + c0 / 4 + 4 * ld_ + (kdim - 1) * pitch;
@@ -1342,7 +1361,7 @@ __global__ __launch_bounds__(768, 1) void k_syrk_h2s(const uint8_t* __restrict__
         if ((s & 1) && sf.due(s + 1 < nst)) sf.flush(acc);
     }
     sf.finish(acc);
-    epilogue_pi<LOCAL>(acc, tiles, n, bi, bj, accumulate, lane, wm, wn, blk);
+    epilogue_pi<LOCAL || RECT>(acc, tiles, n, bi, bj, accumulate, lane, wm, wn, blk);
     sf.release(seg);
 }
 
@@ -1358,13 +1377,19 @@ struct PRegs {
     double l[4];
 };
 
-// packed: op = t>>7; 128 threads cover BK=16 SNPs x 8 dwords.
+// packed: op = t>>7; 128 threads cover BK=16 SNPs x 8 dwords.  Pb (two-operand form): the B
+// panel's threads read the second operand.
 __device__ __forceinline__ void load_packed(const uint8_t* __restrict__ P, uint64_t pitch, uint64_t kdim, uint64_t k0,
-                                            uint64_t i0, uint64_t j0, const double* __restrict__ lut, PRegs& r) {
+                                            uint64_t i0, uint64_t j0, const double* __restrict__ lut, PRegs& r,
+                                            const uint8_t* __restrict__ Pb = nullptr, uint64_t pitch_b = 0) {
     const int t = threadIdx.x;
     const int op = t >> 7, tt = t & 127;
     const int k = tt >> 3, d = tt & 7;
     const uint64_t base = op ? j0 : i0;
+    if (Pb && op) {
+        P = Pb;
+        pitch = pitch_b;
+    }
     const uint64_t kk = k0 + k;
     if (kk < kdim) {
         r.w = *reinterpret_cast<const uint32_t*>(P + kk * pitch + base / 4 + 4 * d);
@@ -1501,16 +1526,28 @@ __device__ __forceinline__ void epilogue(f64x4 (&acc)[4][4], double* __restrict_
 // "f64" = 1): 128x128 tiles, 4 waves; the select of stage s+1's values is interleaved with stage s's
 // MFMAs and stored bank-rotated (compute_store): 60.5 TFLOP/s = 0.77 of 78.6 at N = 32768
 // (tools/ubench.py syrk --dtype f64).  part_tab (cfg5): quadrant q of slot w of the part's layout.
+template <bool RECT = false>
 __global__ __launch_bounds__(256, 2) void k_syrk(const uint8_t* __restrict__ src, uint64_t ld, uint64_t kdim,
                                                  const double* __restrict__ lut, double* __restrict__ tiles,
                                                  int accumulate, const int* __restrict__ gate = nullptr,
-                                                 const uint32_t* __restrict__ part_tab = nullptr) {
+                                                 const uint32_t* __restrict__ part_tab = nullptr,
+                                                 RectArg<RECT> rb = RectArg<RECT>()) {
     __shared__ __attribute__((aligned(16))) double lds[2][2][BK * LDA];
     if (gate && *gate == 0) return;  // fallback of the CRT path: runs only when its flag is set
     uint32_t ti, tj;
     double* T;
     uint64_t ldo = BM;
-    if (part_tab) {  // cfg5: quadrant q of slot w of the part's layout, written into its dense block
+    const uint8_t* srcb = nullptr;
+    uint64_t ldb = 0;
+    if constexpr (RECT) {  // two operands: quadrant q of block w = bj * nba + bi of the rectangle
+        const uint64_t w = blockIdx.x >> 2, q = blockIdx.x & 3;
+        ti = 2 * (uint32_t)(w % rb.nba) + (uint32_t)(q & 1);
+        tj = 2 * (uint32_t)(w / rb.nba) + (uint32_t)(q >> 1);
+        T = tiles + w * 65536 + (q & 1) * 128 * 256 + (q >> 1) * 128;
+        ldo = 256;
+        srcb = rb.P;
+        ldb = rb.pitch;
+    } else if (part_tab) {  // cfg5: quadrant q of slot w of the part's layout, written into its dense block
         const uint64_t w = blockIdx.x >> 2, q = blockIdx.x & 3;
         ti = 2 * (part_tab[w] & 0xffffu) + (uint32_t)(q & 1);
         tj = 2 * (part_tab[w] >> 16) + (uint32_t)(q >> 1);
@@ -1531,13 +1568,13 @@ __global__ __launch_bounds__(256, 2) void k_syrk(const uint8_t* __restrict__ src
 
     const uint64_t nst = (kdim + BK - 1) / BK;
     PRegs rp;
-    load_packed(src, ld, kdim, 0, i0, j0, lut, rp);
+    load_packed(src, ld, kdim, 0, i0, j0, lut, rp, srcb, ldb);
     store_packed(lds[0][0], lds[0][1], rp);
     __syncthreads();
     for (uint64_t s = 0; s < nst; s++) {
         const int buf = s & 1;
         const bool more = s + 1 < nst;
-        if (more) load_packed(src, ld, kdim, (s + 1) * BK, i0, j0, lut, rp);
+        if (more) load_packed(src, ld, kdim, (s + 1) * BK, i0, j0, lut, rp, srcb, ldb);
         compute_store(lds[buf][0], lds[buf][1], acc, wm, wn, lane, lds[buf ^ 1][0], lds[buf ^ 1][1], rp, more);
         __syncthreads();
     }
@@ -1640,7 +1677,7 @@ void launch_syrk_packed(const uint8_t* packed, uint64_t pitch, uint64_t n, uint6
     // tools/ubench.py syrk --dtype f64 (N=32768, 8192 SNPs): plain loader 51.3 TFLOP/s, select
     // interleaved with the MFMAs 56.1, that + bank-rotated LDS stores 60.5 (77% of 78.6); MFMA-only
     // ablation 71.5.
-    f64k::k_syrk<<<(unsigned)g, 256, 0, st>>>(packed, pitch, m, (const double*)lut, (double*)o.k, accumulate, gate, o.tab);
+    f64k::k_syrk<><<<(unsigned)g, 256, 0, st>>>(packed, pitch, m, (const double*)lut, (double*)o.k, accumulate, gate, o.tab);
     SNPMI_HIP(hipGetLastError());
 }
 
@@ -1834,6 +1871,56 @@ static void launch_f32_chain(const uint8_t* packed, uint64_t pitch, uint64_t n, 
 static void check_chain_pitch(uint64_t pitch, uint64_t n) {
     SNPMI_REQUIRE(pitch % 64 == 0 && pitch * 4 >= ceil_div(n, 256) * 256, SNPMI_E_ARG,
                   "packed pitch must cover round_up(n, 256) iids");
+}
+
+// Two-operand ("rect") GRM: K[rows, cols] of two packed operands over the same SNP rows, as dense
+// 256 x 256 blocks, block (bi, bj) at slot bj * nba + bi -- bi fastest, so the blocks in flight share
+// one B panel (or two) and the few A panels of a wide-and-short rectangle stay in L2.  No split-K:
+// a rectangle of a few blocks leaves most CUs idle.  Returns the block count after the limit checks.
+uint64_t rect_blocks(uint64_t n_a, uint64_t pitch_a, uint64_t n_b, uint64_t pitch_b) {
+    const uint64_t nba = ceil_div(n_a, 256), nbb = ceil_div(n_b, 256);
+    SNPMI_REQUIRE(nba < 65536 && nbb < 65536 && nba * nbb < (1ull << 29), SNPMI_E_ARG,
+                  "rect GRM: too many 256-iid blocks for one launch");
+    check_chain_pitch(pitch_a, n_a);
+    check_chain_pitch(pitch_b, n_b);
+    return nba * nbb;
+}
+
+// f32: the fp16x2 kernel and the bf16x3 kernel gated on its range flag (h2 == nullptr: bf16x3 alone)
+void launch_syrk_rect_f32(const uint8_t* Pa, uint64_t pitch_a, uint64_t n_a, const uint8_t* Pb, uint64_t pitch_b,
+                          uint64_t n_b, uint64_t m, const uint32_t* lut3, const H2Lut* h2, float* blocks,
+                          int accumulate, hipStream_t st) {
+    const uint64_t g = rect_blocks(n_a, pitch_a, n_b, pitch_b);
+    if (g == 0) return;
+    if (m == 0) {
+        if (!accumulate) SNPMI_HIP(hipMemsetAsync(blocks, 0, g * 65536 * sizeof(float), st));
+        return;
+    }
+    const SegCtx seg = seg_ctx();
+    const RectArg<true> rb{Pb, pitch_b, (uint32_t)ceil_div(n_a, 256), nullptr};
+    if (h2) {
+        f32w::k_syrk_h2s<false, true><<<(unsigned)g, 768, 0, st>>>(Pa, pitch_a, n_a, m, h2->lut2, h2->flag, blocks,
+                                                                  accumulate, 0, 1, 0, 0, seg, nullptr, 0, rb);
+        SNPMI_HIP(hipGetLastError());
+    }
+    f32w::k_syrk_bf3<false, true><<<(unsigned)g, 512, 0, st>>>(Pa, pitch_a, n_a, m, lut3, blocks, accumulate, 0, 1, 0, 0,
+                                                              h2 ? h2->flag : nullptr, seg, 0, nullptr, rb);
+    SNPMI_HIP(hipGetLastError());
+}
+
+// f64 on the f64 MFMA (the CRT path's fallback: gate = its non-finite flag, or nullptr: always)
+void launch_syrk_rect_f64(const uint8_t* Pa, uint64_t pitch_a, uint64_t n_a, const uint8_t* Pb, uint64_t pitch_b,
+                          uint64_t n_b, uint64_t m, const double* lut, double* blocks, int accumulate, hipStream_t st,
+                          const int* gate) {
+    const uint64_t g = rect_blocks(n_a, pitch_a, n_b, pitch_b);
+    if (g == 0 || (gate && m == 0)) return;
+    if (m == 0) {
+        if (!accumulate) SNPMI_HIP(hipMemsetAsync(blocks, 0, g * 65536 * sizeof(double), st));
+        return;
+    }
+    const RectArg<true> rb{Pb, pitch_b, (uint32_t)ceil_div(n_a, 256), nullptr};
+    f64k::k_syrk<true><<<(unsigned)(4 * g), 256, 0, st>>>(Pa, pitch_a, m, lut, blocks, accumulate, gate, nullptr, rb);
+    SNPMI_HIP(hipGetLastError());
 }
 
 // the chain over all of a destination's blocks

@@ -194,10 +194,12 @@ __global__ __launch_bounds__(256) void k_crt_panels(const double* __restrict__ S
 }
 
 // moduli the 256-block (bi, bj) needs (1 <= R_b <= ctl[2]); the same formula as k_crt_r's
+// lgpb: the bound table of block column bj's operand (the two-operand form: |K_int,ij| <=
+// sqrt(S_i(A) S_j(B)) by the same argument; lgpb == lgp for the SYRK)
 __device__ __forceinline__ int block_moduli(const double* __restrict__ lgp, uint32_t bi, uint32_t bj, const CrtLog& L,
-                                            const int* __restrict__ ctl) {
+                                            const int* __restrict__ ctl, const double* __restrict__ lgpb) {
     if (!L.per_block) return ctl[2];
-    const double need = 0.5 * (lgp[bi] + lgp[bj]) + 1.0;
+    const double need = 0.5 * (lgp[bi] + lgpb[bj]) + 1.0;
     int R = 1;
     while (R < kR && L.plog[R - 1] <= need) R++;
     return R;
@@ -272,7 +274,7 @@ __global__ __launch_bounds__(512, 1) void k_syrk_i8r(const uint8_t* __restrict__
     } else {
         tile_coords(b0 + bx, bi, bj);
     }
-    if ((int)r >= block_moduli(lgp, bi, bj, L, ctl)) return;  // this block's K_int fits the first R_b moduli
+    if ((int)r >= block_moduli(lgp, bi, bj, L, ctl, lgp)) return;  // this block's K_int fits the first R_b moduli
     const uint64_t i0 = (uint64_t)bi * BW, j0 = (uint64_t)bj * BW;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wm = wave >> 2, wn = wave & 3;
@@ -390,12 +392,13 @@ __global__ __launch_bounds__(512, 1) void k_syrk_i8r(const uint8_t* __restrict__
 // selector byte per iid by a per-launch pre-pass (no shift / mask VALU in the loader, 4x the code
 // bytes) +32%; the loader's code loads issued two stages ahead (two register sets) +2.8%, issued
 // one stage ahead but before the stores instead of after them +13%.
-template <int SKT, bool ROTA = true, int MPRIO = 2>
+template <int SKT, bool ROTA = true, int MPRIO = 2, bool RECT = false>
 __global__ __launch_bounds__(768, 1) void k_syrk_i8w(const uint8_t* __restrict__ P, uint64_t pitch, uint64_t kdim,
                                                      uint64_t mpad, const uint32_t* __restrict__ lutr,
                                                      const int* __restrict__ ctl, uint64_t b0, uint64_t nblk,
                                                      uint8_t* __restrict__ res, const double* __restrict__ lgp, CrtLog L,
-                                                     const uint32_t* __restrict__ part_tab = nullptr) {
+                                                     const uint32_t* __restrict__ part_tab = nullptr,
+                                                     RectArg<RECT> rb = RectArg<RECT>()) {
     constexpr int KS = SKT / 32, RPL = SKT / 8, PNL = SKT * RS, STG = 2 * PNL;
     __shared__ __attribute__((aligned(16))) uint8_t lds[2 * STG];
     if (ctl[1]) return;  // non-finite LUT: the f64 MFMA kernel runs instead
@@ -403,14 +406,19 @@ __global__ __launch_bounds__(768, 1) void k_syrk_i8w(const uint8_t* __restrict__
     const uint32_t r = q - u * kR, bx = 8 * u + (w & 7);
     if (bx >= nblk) return;
     uint32_t bi, bj;
-    if (part_tab) {
+    const double* lgpb = lgp;
+    if constexpr (RECT) {  // two operands: block b0 + bx = bj * nba + bi of the rectangle
+        bi = (uint32_t)((b0 + bx) % rb.nba);
+        bj = (uint32_t)((b0 + bx) / rb.nba);
+        lgpb = rb.lgp;
+    } else if (part_tab) {
         const uint32_t c = part_tab[b0 + bx];
         bi = c & 0xffffu;
         bj = c >> 16;
     } else {
         tile_coords(b0 + bx, bi, bj);
     }
-    if ((int)r >= block_moduli(lgp, bi, bj, L, ctl)) return;  // this block's K_int fits the first R_b moduli
+    if ((int)r >= block_moduli(lgp, bi, bj, L, ctl, lgpb)) return;  // this block's K_int fits the first R_b moduli
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const uint64_t nst = (kdim + SKT - 1) / SKT;
@@ -418,6 +426,12 @@ __global__ __launch_bounds__(768, 1) void k_syrk_i8w(const uint8_t* __restrict__
         // loader: thread lt = (panel lp, row block kq of RPL rows, 16-iid group d)
         const int lt = t - 512;
         const int lp = __builtin_amdgcn_readfirstlane(lt >> 7), kq = (lt >> 4) & 7, d = lt & 15;
+        if constexpr (RECT) {  // the B panel's loader waves read the second operand
+            if (lp) {
+                P = rb.P;
+                pitch = rb.pitch;
+            }
+        }
         const uint8_t* pbase = P + (uint64_t)(lp ? bj : bi) * (BW / 4);
         const uint32_t pit = (uint32_t)pitch;
         const uint32_t* lq = lutr + (uint64_t)r * mpad + RPL * kq;
@@ -602,24 +616,31 @@ __device__ __forceinline__ void digits(f2 (&v)[2][kR], const uint8_t* __restrict
 // one 4-B load per residue plane and thread, two independent packed-f32 Garner chains
 // part (cfg5): the block of slot b0 + blk is written whole (256 x 256 row-major, f64) at
 // tiles + (b0 + blk) * 65536, as the f32 part kernels write theirs
+template <bool RECT = false>
 __global__ __launch_bounds__(256) void k_crt(const uint8_t* __restrict__ res, uint64_t b0, uint64_t nblk, uint64_t n,
                                              const int* __restrict__ ctl, int F, CrtConst cc, double* __restrict__ tiles,
                                              int accumulate, const uint32_t* __restrict__ part_tab,
                                              const double* __restrict__ lgp, CrtLog L,
-                                             unsigned long long* __restrict__ rec) {
+                                             unsigned long long* __restrict__ rec,
+                                             RectArg<RECT> rb = RectArg<RECT>()) {
     if (ctl[1]) return;
     const uint64_t blk = blockIdx.x >> 6;
     const int row = 4 * (blockIdx.x & 63) + (threadIdx.x >> 6), col = 4 * (threadIdx.x & 63);
-    const bool part = part_tab != nullptr;
+    const bool part = RECT || part_tab != nullptr;  // whole dense blocks at slot b0 + blk
     uint32_t bi, bj;
-    if (part) {
+    const double* lgpb = lgp;
+    if constexpr (RECT) {
+        bi = (uint32_t)((b0 + blk) % rb.nba);
+        bj = (uint32_t)((b0 + blk) / rb.nba);
+        lgpb = rb.lgp;
+    } else if (part) {
         const uint32_t c = part_tab[b0 + blk];
         bi = c & 0xffffu;
         bj = c >> 16;
     } else {
         tile_coords(b0 + blk, bi, bj);
     }
-    const int R = block_moduli(lgp, bi, bj, L, ctl);  // the moduli k_syrk_i8* ran for this block
+    const int R = block_moduli(lgp, bi, bj, L, ctl, lgpb);  // the moduli k_syrk_i8* ran for this block
     if (rec && (blockIdx.x & 63) == 0 && threadIdx.x == 0) {
         atomicAdd(rec + 2, (unsigned long long)R);
         atomicAdd(rec + 3, 1ull);
@@ -793,13 +814,65 @@ void launch_syrk_packed_crt(const uint8_t* packed, uint64_t pitch, uint64_t n, u
         else
             k_syrk_i8r<SK><<<(unsigned)(round_up(cnt, 8) * kR), 512, 0, st>>>(packed, pitch, m, mpad, lutr, ctl, b0,
                                                                             cnt, res, lgp, logs, part_tab);
-        k_crt<<<(unsigned)(cnt * 64), 256, 0, st>>>(res, b0, cnt, n, ctl, F, cc, tiles, accumulate, part_tab, lgp, logs,
+        k_crt<><<<(unsigned)(cnt * 64), 256, 0, st>>>(res, b0, cnt, n, ctl, F, cc, tiles, accumulate, part_tab, lgp, logs,
                                                     rec);
         if (after_chunk) {
             SNPMI_HIP(hipGetLastError());
             (*after_chunk)(cols[ci].first, cols[ci].second);
             ci++;
         }
+    }
+    SNPMI_HIP(hipGetLastError());
+}
+
+// ctl | residue LUT | bound table | per-iid bound sums of A, then B | per-panel log2 bounds of A, then B
+uint64_t crt_rect_lut_bytes(uint64_t m, uint64_t n_a, uint64_t n_b) {
+    const uint64_t mpad = round_up(std::max<uint64_t>(m, 1), SK);
+    return 256 + (uint64_t)kR * mpad * 4 + mpad * 32 + (round_up(n_a, 2) + round_up(n_b, 2) + 2) * 8 +
+           (round_up(ceil_div(n_a, BW), 2) + round_up(ceil_div(n_b, BW), 2) + 2) * 8;
+}
+
+// The two-operand form of launch_syrk_packed_crt: blocks (+)= Za Zb^T as the dense 256 x 256 blocks
+// of the rectangle (slot bj * nba + bi).  The LUT tables are built once; the bound sums and panel
+// bounds once per operand (k_crt_bound, k_crt_panels).  The launch-wide R of hook "crt_block" = 0
+// comes from the larger of the two operands' maxima (sqrt(Ma Mb) <= max(Ma, Mb)).
+void launch_syrk_rect_crt(const uint8_t* Pa, uint64_t pitch_a, uint64_t n_a, const uint8_t* Pb, uint64_t pitch_b,
+                          uint64_t n_b, uint64_t m, const double* lut, double* blocks, int accumulate, void* ws_lut,
+                          uint8_t* res, uint64_t res_bytes, unsigned long long* rec, hipStream_t st) {
+    SNPMI_REQUIRE(m > 0 && m <= crt_max_snps(), SNPMI_E_ARG, "crt SYRK: SNP count per launch out of range");
+    const uint64_t total = rect_blocks(n_a, pitch_a, n_b, pitch_b);
+    if (total == 0) return;
+    const uint64_t nba = ceil_div(n_a, BW), nbb = ceil_div(n_b, BW), mpad = round_up(m, SK);
+    int* ctl = (int*)ws_lut;
+    uint32_t* lutr = (uint32_t*)((uint8_t*)ws_lut + 256);
+    double* qsq = (double*)(lutr + (uint64_t)kR * mpad);
+    double* Sa = qsq + 4 * mpad;
+    double* Sb = Sa + round_up(n_a, 2);
+    double* lga = Sb + round_up(n_b, 2);
+    double* lgb = lga + round_up(nba, 2);
+    const int F = crt_fraction_bits(m);
+    k_crt_exp<<<1, 1024, 0, st>>>(lut, 4 * m, ctl);
+    k_crt_lut<<<(unsigned)ceil_div(mpad, 256), 256, 0, st>>>(lut, m, mpad, F, ctl, lutr, qsq);
+    SNPMI_HIP(hipMemsetAsync(Sa, 0, (round_up(n_a, 2) + round_up(n_b, 2)) * sizeof(double), st));
+    k_crt_bound<<<dim3((unsigned)ceil_div(ceil_div(n_a, 16), 256), (unsigned)ceil_div(m, kBoundSlice)), 256, 0, st>>>(
+        Pa, pitch_a, n_a, m, qsq, ctl, Sa);
+    k_crt_bound<<<dim3((unsigned)ceil_div(ceil_div(n_b, 16), 256), (unsigned)ceil_div(m, kBoundSlice)), 256, 0, st>>>(
+        Pb, pitch_b, n_b, m, qsq, ctl, Sb);
+    static const CrtLog logs0 = crt_logs();
+    CrtLog logs = logs0;
+    logs.per_block = g_crt_block;
+    k_crt_r<<<1, 1024, 0, st>>>(Sa, round_up(n_a, 2) + n_b, logs, ctl, rec);
+    k_crt_panels<<<(unsigned)nba, 256, 0, st>>>(Sa, n_a, ctl, lga);
+    k_crt_panels<<<(unsigned)nbb, 256, 0, st>>>(Sb, n_b, ctl, lgb);
+    const uint64_t per = std::min<uint64_t>(std::max<uint64_t>(1, res_bytes / ((uint64_t)kR * BW * BW)), (1ull << 23) - 8);
+    static const CrtConst cc = crt_constants();
+    const RectArg<true> rb{Pb, pitch_b, (uint32_t)nba, lgb};
+    for (uint64_t b0 = 0, cnt = 0; b0 < total; b0 += cnt) {
+        cnt = std::min(per, total - b0);
+        k_syrk_i8w<SK, true, 2, true><<<(unsigned)(round_up(cnt, 8) * kR), 768, 0, st>>>(Pa, pitch_a, m, mpad, lutr, ctl, b0,
+                                                                                       cnt, res, lga, logs, nullptr, rb);
+        k_crt<true><<<(unsigned)(cnt * 64), 256, 0, st>>>(res, b0, cnt, n_a, ctl, F, cc, blocks, accumulate, nullptr, lga,
+                                                         logs, rec, rb);
     }
     SNPMI_HIP(hipGetLastError());
 }

@@ -103,7 +103,15 @@ class SnpKernel(KernelReader):
         if pk is not None:
             return pk._read(row_index_or_none, col_index_or_none, order, dtype, force_python_only, view_ok,
                             num_threads)
-        whole = self.snpreader._read_kernel(self.standardizer, self.block_size, order, dtype, force_python_only,
+        if row_index_or_none is not None or col_index_or_none is not None:
+            # K[rows, cols] directly (set_grm_rect): the rectangle's blocks only, never the whole K
+            from pysnptools_amd.kernelreader.rect import read_rect
+
+            val = read_rect(self.snpreader, self.standardizer, row_index_or_none, col_index_or_none, order, dtype,
+                            num_threads)
+            if val is not None:
+                return val
+        whole =self.snpreader._read_kernel(self.standardizer, self.block_size, order, dtype, force_python_only,
                                             view_ok, num_threads=num_threads)
         val, _ = self._apply_sparray_or_slice_to_val(whole, row_index_or_none, col_index_or_none, order, dtype,
                                                      force_python_only, num_threads)

@@ -1,0 +1,365 @@
+"""K[rows, cols] computed directly (the two-operand "rect" GRM kernels, snpmi_dev_syrk_rect /
+snpmi_grm_rect_*, SnpKernel under set_grm_rect) against the f64 oracle.
+
+Error measure: max|K - ref| / max_i (Z Z^T)_ii, as grm_close; f32 <= 1e-5 (the README's f32 parity
+bar), f64 <= 1e-12 (test_gpu_cfg4_full.py).  Shapes are the smallest that reach the edges: 1101 iids
+(n % 4 = 1), 1000 SNPs (no multiple of the 32-SNP stage), 300 rows (blocks of 256 + 44, unsorted,
+one repeated) x 700 cols (3 blocks, 150 shared with the rows).
+"""
+import os
+
+import numpy as np
+import pytest
+
+from conftest import DATA  # noqa: F401  (sys.path)
+import bench
+from oracle import oracle as O
+from pysnptools_amd import _native as N
+
+pytestmark = pytest.mark.gpu
+
+n, m, m2 = 1101, 1000, 37
+TOL = {np.dtype(np.float32): 1e-5, np.dtype(np.float64): 1e-12}
+
+
+def _indices():
+    rng = np.random.RandomState(7)
+    perm = rng.permutation(n)
+    rows = perm[:300].copy()
+    rows[17] = rows[3]  # one repeated index
+    cols = np.concatenate([rows[:150], perm[300:850]])
+    rng.shuffle(cols)
+    return rows.astype(np.uint64), cols.astype(np.uint64)
+
+
+ROWS, COLS = _indices()
+
+
+@pytest.fixture(scope="module")
+def data():
+    """packed codes of m + m2 SNPs on the device, and the oracle's standardized Z in f64 (per
+    SNP, so Z[:, :m] is also the standardization of the first m alone)."""
+    mt = m + m2
+    pitch = N.lib().snpmi_packed_pitch(n)
+    packed = bench.Dev(N, pitch * mt)
+    bench.synth(N, packed.p, pitch, n, 0, mt, 23, 0.05)
+    host = np.empty((mt, pitch), dtype=np.uint8)
+    N.call("snpmi_memcpy_d2h", N.ptr(host), packed.p, host.nbytes)
+    body = np.ascontiguousarray(host[:, :(n + 3) // 4]).reshape(-1)
+    Z, _ = O.decode_standardize(body, n, mt, dtype=np.float64)
+    yield packed, pitch, np.ascontiguousarray(Z)
+    packed.free()
+
+
+def _err(K, ref, Z):
+    scale = np.einsum("ij,ij->i", Z, Z).max()
+    return np.abs(np.asarray(K, dtype=np.float64) - ref).max() / scale
+
+
+def _operand(packed, pitch, idx, cnt):
+    """(device buffer or None, pointer, pitch): the codes repacked to idx, or in place for None."""
+    if idx is None:
+        return None, packed.p, pitch
+    po = N.lib().snpmi_packed_pitch(len(idx))
+    didx, dst = bench.Dev(N, len(idx) * 8), bench.Dev(N, po * cnt)
+    N.call("snpmi_memcpy_h2d", didx.p, N.ptr(idx), idx.nbytes)
+    N.call("snpmi_dev_repack", packed.p, pitch, n, didx.p, len(idx), cnt, dst.p, po)
+    N.call("snpmi_stream_sync")
+    didx.free()
+    return dst, dst.p, po
+
+
+def _stateless(packed, pitch, rows, cols, dtype, cnt=m, exact_diag=True):
+    from pysnptools_amd.kernelreader.rect import diag_pairs
+
+    dtype = np.dtype(dtype)
+    nr, nc = (n if rows is None else len(rows)), (n if cols is None else len(cols))
+    lut, stats = bench.Dev(N, cnt * 4 * dtype.itemsize), bench.Dev(N, cnt * 2 * dtype.itemsize)
+    N.call("snpmi_dev_snp_stats", packed.p, pitch, n, cnt, 0, N.STD_UNIT, 0.0, 0.0, 0, N.dt_code(dtype), stats.p, lut.p)
+    a, pa, pitch_a = _operand(packed, pitch, rows, cnt)
+    b, pb, pitch_b = _operand(packed, pitch, cols, cnt)
+    nbytes = int(N.lib().snpmi_grm_rect_bytes(nr, nc, N.dt_code(dtype)))
+    assert nbytes == -(-nr // 256) * -(-nc // 256) * 65536 * dtype.itemsize
+    blocks = bench.Dev(N, nbytes)
+    pairs = diag_pairs(rows, cols, nr, nc) if exact_diag else np.empty((0, 2), np.uint32)
+    K = np.empty((nr, nc), dtype=dtype)
+    try:
+        N.call("snpmi_dev_syrk_rect", pa, pitch_a, nr, pb, pitch_b, nc, cnt, lut.p, N.dt_code(dtype), blocks.p, 0,
+               N.ptr(pairs) if len(pairs) else None, len(pairs))
+        N.call("snpmi_dev_rect_extract", blocks.p, nr, nc, N.dt_code(dtype), 1, 1.0, N.ptr(K))
+    finally:
+        for d in (lut, stats, blocks, a, b):
+            if d is not None:
+                d.free()
+    return K
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_stateless_launch_vs_oracle(data, dtype):
+    packed, pitch, Zall = data
+    Z = Zall[:, :m]
+    K = _stateless(packed, pitch, ROWS, COLS, dtype)
+    e = _err(K, Z[ROWS] @ Z[COLS].T, Z)
+    print("rows x cols", np.dtype(dtype).name, e)
+    assert e <= TOL[np.dtype(dtype)], e
+    Kall = _stateless(packed, pitch, None, COLS, dtype)  # the in-place operand
+    e = _err(Kall, Z @ Z[COLS].T, Z)
+    print("all x cols", np.dtype(dtype).name, e)
+    assert e <= TOL[np.dtype(dtype)], e
+    Kt = _stateless(packed, pitch, COLS, ROWS, dtype)  # the transpose request
+    e = _err(Kt, Z[COLS] @ Z[ROWS].T, Z)
+    print("cols x rows", np.dtype(dtype).name, e)
+    assert e <= TOL[np.dtype(dtype)], e
+    if np.dtype(dtype) == np.float64:  # exact integer sums: the same bits either way round
+        assert np.array_equal(K, Kt.T)
+
+
+@pytest.mark.parametrize("cnt", [31, 32, 33, m])
+def test_segment_flush(data, cnt):
+    """SegFlush in the two-operand fp16x2 kernel: 256-SNP segments (a flush every 4 trips), and
+    SNP counts around one 32-SNP stage."""
+    packed, pitch, Zall = data
+    Z = Zall[:, :cnt]
+    seg_default = N.kernel_variant("seg")
+    N.call("snpmi_set_kernel_variant", b"seg", 256)
+    try:
+        K = _stateless(packed, pitch, ROWS, COLS, np.float32, cnt=cnt)
+    finally:
+        N.call("snpmi_set_kernel_variant", b"seg", seg_default)
+    e = _err(K, Z[ROWS] @ Z[COLS].T, Z)
+    print("seg 256, m", cnt, e)
+    assert e <= 1e-5, e
+
+
+def _session(packed, pitch, dtype, parts, rows, cols, order_c=1):
+    dtype = np.dtype(dtype)
+    sfx = N.suffix(dtype)
+    nr, nc = (n if rows is None else len(rows)), (n if cols is None else len(cols))
+    K = np.full((nr, nc), 7.0, dtype=dtype, order="C" if order_c else "F")
+    N.call("snpmi_grm_rect_begin", nr, nc, N.dt_code(dtype))
+    try:
+        for s0, cnt in parts:
+            st = np.empty((cnt, 2), dtype=dtype)
+            N.call("snpmi_grm_rect_add_packed_" + sfx, packed.at(s0 * pitch), pitch, n, cnt, 0, N.STD_UNIT, 0.0, 0.0, 0,
+                   N.ptr(st), N.ptr(rows), N.ptr(cols))
+    finally:
+        N.call("snpmi_grm_rect_end", 1.0, order_c, N.ptr(K) if K.size else None)
+    return K
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_session_accumulates(data, dtype):
+    packed, pitch, Z = data
+    K = _session(packed, pitch, dtype, [(0, m), (m, m2)], ROWS, COLS)
+    e = _err(K, Z[ROWS] @ Z[COLS].T, Z)
+    print("1000 + 37", np.dtype(dtype).name, e)
+    assert e <= TOL[np.dtype(dtype)], e
+    Kf = _session(packed, pitch, dtype, [(0, m), (m, m2)], ROWS, COLS, order_c=0)
+    assert Kf.flags["F_CONTIGUOUS"] and np.array_equal(Kf, K)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_session_empty_cases(data, dtype):
+    packed, pitch, _ = data
+    none = np.empty(0, dtype=np.uint64)
+    assert _session(packed, pitch, dtype, [(0, m)], none, COLS).shape == (0, len(COLS))
+    assert _session(packed, pitch, dtype, [(0, m)], ROWS, none).shape == (len(ROWS), 0)
+    K = _session(packed, pitch, dtype, [(0, 0)], ROWS, COLS)
+    assert K.shape == (len(ROWS), len(COLS)) and not K.any()
+    K = _session(packed, pitch, dtype, [], ROWS, COLS)
+    assert not K.any()
+
+
+def test_bad_index_and_pitch(data):
+    packed, pitch, _ = data
+    bad = ROWS.copy()
+    bad[5] = n
+    with pytest.raises(IndexError):
+        _session(packed, pitch, np.float32, [(0, m)], bad, COLS)
+    with pytest.raises(IndexError):
+        _session(packed, pitch, np.float64, [(0, m)], ROWS, np.array([n + 3], dtype=np.uint64))
+    # 300 iids need a pitch of 128 bytes (round_up(300, 256) iids): 64 does not cover them
+    lut, blocks = bench.Dev(N, m * 16), bench.Dev(N, int(N.lib().snpmi_grm_rect_bytes(300, 300, N.DT_F32)))
+    try:
+        with pytest.raises(ValueError):
+            N.call("snpmi_dev_syrk_rect", packed.p, 64, 300, packed.p, pitch, 300, m, lut.p, N.DT_F32, blocks.p, 0, None, 0)
+        with pytest.raises(ValueError):
+            N.call("snpmi_dev_syrk_rect", packed.p, pitch, 300, packed.p, 100, 300, m, lut.p, N.DT_F64, blocks.p, 0, None, 0)
+    finally:
+        lut.free()
+        blocks.free()
+
+
+# ------------------------------------------------------------------------------- SnpKernel
+def bed(name, count_A1=False):
+    from pysnptools_amd.snpreader import Bed
+
+    return Bed(os.path.join(DATA, name + ".bed"), count_A1=count_A1)
+
+
+@pytest.fixture()
+def rect_always():
+    from pysnptools_amd.kernelreader import rect
+
+    old = rect.grm_rect_mode()
+    rect.set_grm_rect("always")
+    yield
+    rect.set_grm_rect(old)
+
+
+def _oracle_z(name, count_A1, iid_index=None, sid_index=None):
+    path = os.path.join(DATA, name + ".bed")
+    ni, ns = O.bed_shape(path)
+    return O.decode(O.read_bed_bytes(path), ni, ns, count_A1=count_A1, iid_index=iid_index, sid_index=sid_index,
+                    order="F", dtype=np.float64)
+
+
+def _toy_idx(nn, seed=3):
+    rng = np.random.RandomState(seed)
+    perm = rng.permutation(nn)
+    rows = perm[:70].copy()
+    rows[5] = rows[1]
+    cols = np.concatenate([rows[:30], perm[70:70 + 290]])
+    rng.shuffle(cols)
+    return rows, cols
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("count_A1", [False, True])
+@pytest.mark.parametrize("std_name", ["unit", "beta", "trained"])
+def test_snpkernel_rect_vs_oracle(rect_always, std_name, count_A1, dtype):
+    from pysnptools_amd.kernelreader import SnpKernel
+    from pysnptools_amd.standardizer import Beta, Unit, UnitTrained
+
+    b = bed("toydata", count_A1)
+    Z = _oracle_z("toydata", count_A1)
+    if std_name == "beta":
+        std = Beta(1, 25)
+        O.standardize_native(Z, is_beta=True, a=1, b=25)
+    else:
+        stats = O.standardize_native(Z)
+        std = Unit() if std_name == "unit" else UnitTrained(b.sid, stats)
+    rows, cols = _toy_idx(b.iid_count)
+    ref = Z[rows] @ Z[cols].T
+    for order in ("C", "F"):
+        K = SnpKernel(b, std)[rows, cols].read(order=order, dtype=dtype).val
+        assert K.shape == ref.shape and K.dtype == np.dtype(dtype) and K.flags[order + "_CONTIGUOUS"]
+        e = _err(K, ref, Z)
+        print(std_name, count_A1, np.dtype(dtype).name, order, e)
+        assert e <= TOL[np.dtype(dtype)], e
+    if np.dtype(dtype) == np.float64:
+        # the same launch boundaries and exact integer sums as the whole-K path: the same bits
+        whole = b.read_kernel(std, dtype=np.float64).val
+        assert np.array_equal(K, whole[np.ix_(rows, cols)])
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_snpkernel_rect_on_subset_reader(rect_always, dtype):
+    """bed[iid_sel, 100:2100]: the stats are over iid_sel only, rows / cols index into iid_sel."""
+    from pysnptools_amd.kernelreader import SnpKernel
+    from pysnptools_amd.standardizer import Unit
+
+    b = bed("toydata")
+    iid_sel = np.random.RandomState(11).permutation(b.iid_count)[:333]
+    sub = b[iid_sel, 100:2100]
+    Z = _oracle_z("toydata", False, iid_index=iid_sel, sid_index=np.arange(100, 2100))
+    O.standardize_native(Z)
+    rows, cols = _toy_idx(len(iid_sel), seed=5)
+    cols = cols[:200]
+    K = SnpKernel(sub, Unit())[rows, cols].read(dtype=dtype).val
+    e = _err(K, Z[rows] @ Z[cols].T, Z)
+    print("subset", np.dtype(dtype).name, e)
+    assert e <= TOL[np.dtype(dtype)], e
+    if np.dtype(dtype) == np.float64:
+        assert np.array_equal(K, sub.read_kernel(Unit(), dtype=np.float64).val[np.ix_(rows, cols)])
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_snpkernel_rect_snpgen(rect_always, dtype):
+    from pysnptools_amd.kernelreader import SnpKernel
+    from pysnptools_amd.snpreader import SnpGen
+    from pysnptools_amd.standardizer import Unit
+
+    gen = SnpGen(seed=332, iid_count=500, sid_count=3000)
+    Z = np.array(gen.read(dtype=np.float64, order="F").val, dtype=np.float64, order="F")
+    O.standardize_native(Z)
+    rows, cols = _toy_idx(500, seed=9)
+    K = SnpKernel(gen, Unit())[rows, cols].read(dtype=dtype).val
+    e = _err(K, Z[rows] @ Z[cols].T, Z)
+    print("snpgen", np.dtype(dtype).name, e)
+    assert e <= TOL[np.dtype(dtype)], e
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("name,n_sid,n_rows,n_cols", [("n300", 1015, 90, 270), ("dist_x", 6, 40, 90)])
+def test_identity_nan_pattern(rect_always, name, n_sid, n_rows, n_cols, dtype):
+    """Identity: the NaN pattern is NumPy's for raw[rows] @ raw[cols].T and the finite values are
+    within tolerance.  n300 holds no missing value (an all-finite pattern); the first 6 SNPs of
+    dist_x hold many, so its LUT is non-finite and the fallbacks run (f64: the two-operand f64 MFMA
+    kernel gated on the CRT path's flag; f32: the two-operand bf16x3 kernel on the range flag)."""
+    from pysnptools_amd.kernelreader import SnpKernel
+    from pysnptools_amd.standardizer import Identity
+
+    b = bed(name)[:, :n_sid]
+    raw = _oracle_z(name, False, sid_index=np.arange(n_sid))
+    rng = np.random.RandomState(2)
+    rows, cols = rng.permutation(b.iid_count)[:n_rows], rng.permutation(b.iid_count)[:n_cols]
+    with np.errstate(invalid="ignore"):
+        ref = raw[rows] @ raw[cols].T
+    K = np.asarray(SnpKernel(b, Identity())[rows, cols].read(dtype=dtype).val, dtype=np.float64)
+    assert np.isnan(ref).any() == (name == "dist_x") and not np.isnan(ref).all()
+    assert np.array_equal(np.isnan(K), np.isnan(ref))
+    ok = ~np.isnan(ref)
+    z = np.nan_to_num(raw)
+    e = np.abs(K[ok] - ref[ok]).max() / np.einsum("ij,ij->i", z, z).max()
+    print("identity", name, np.dtype(dtype).name, e)
+    assert e <= TOL[np.dtype(dtype)], e
+
+
+def test_f32_range_fallback(rect_always):
+    """A trained Unit with the std of three SNPs at 1e-7: their values leave fp16's range, the range
+    flag is raised and the two-operand bf16x3 kernel computes the launch."""
+    from pysnptools_amd.kernelreader import SnpKernel
+    from pysnptools_amd.standardizer import UnitTrained
+
+    b = bed("toydata")
+    Z = _oracle_z("toydata", False)
+    stats = O.standardize_native(Z.copy(order="F"))
+    stats[[3, 500, 9999], 1] = 1e-7
+    O.standardize_native(Z, use_stats=True, stats=stats)
+    rows, cols = _toy_idx(b.iid_count)
+    K = SnpKernel(b, UnitTrained(b.sid, stats))[rows, cols].read(dtype=np.float32).val
+    e = _err(K, Z[rows] @ Z[cols].T, Z)
+    print("range fallback", e)
+    assert e <= 1e-5, e
+
+
+def test_hbm_result(rect_always, monkeypatch):
+    from pysnptools_amd import hbm
+    from pysnptools_amd.kernelreader import SnpKernel
+    from pysnptools_amd.standardizer import Unit
+
+    monkeypatch.setenv("ARRAY_MODULE", "hbm")
+    b = bed("toydata")
+    rows, cols = _toy_idx(b.iid_count)
+    val = SnpKernel(b, Unit())[rows, cols].read(dtype=np.float32).val
+    assert isinstance(val, hbm.HbmArray) and val.shape == (len(rows), len(cols))
+
+
+def test_auto_keeps_the_whole_k_route_on_toydata(monkeypatch):
+    from pysnptools_amd.kernelreader import SnpKernel, rect
+    from pysnptools_amd.standardizer import Unit
+
+    assert rect.grm_rect_mode() == "auto"
+    seen = []
+    real = N.call
+
+    def spy(name, *args):
+        seen.append(name)
+        return real(name, *args)
+
+    monkeypatch.setattr(N, "call", spy)
+    b = bed("toydata")
+    rows, cols = _toy_idx(b.iid_count)
+    SnpKernel(b, Unit())[rows, cols].read(dtype=np.float32)
+    assert seen and not [s for s in seen if "rect" in s]
