@@ -760,24 +760,47 @@ static unsigned long long* crt_record(Device& d) {
     return rec;
 }
 
-// f64 GRM on the int8 MFMA residue path (syrk_crt.hip), crt_max_snps() SNPs per step; a step whose
-// LUT holds NaN/Inf is computed by the f64 MFMA kernel instead (gated on the device flag).  A
-// part's residue chunks follow its layout table and K is written as its dense f64 blocks.
-static void syrk_packed_crt(Device& d, const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m,
-                            const double* lut, const GrmDest& o, int accumulate) {
-    // residue scratch: one byte per modulus and element of the 256-blocks, at most 4 GiB (then chunked)
-    const uint64_t res_bytes = std::min<uint64_t>(o.blocks * (uint64_t)crt_moduli() * 65536, 4ull << 30);
-    uint8_t* res = (uint8_t*)d.get(Device::S_ZBLK, res_bytes);
+// Scratch of the CRT path for `blocks` 256-blocks of output: the residues (one byte per modulus and
+// element, at most 4 GiB -- then the launchers chunk), the workspace of one step of <= m SNPs and the
+// moduli counters.  sum_plan cuts the collective from crt_res_bytes, as the launches do.
+static uint64_t crt_res_bytes(uint64_t blocks) {
+    return std::min<uint64_t>(blocks * (uint64_t)crt_moduli() * 65536, 4ull << 30);
+}
+struct CrtScratch {
+    uint8_t* res = nullptr;
+    uint64_t res_bytes = 0;
+    void* ws = nullptr;
+    unsigned long long* rec = nullptr;
+    const int* gate() const { return ws ? (const int*)ws + 1 : nullptr; }  // the non-finite flag
+};
+static CrtScratch crt_scratch(Device& d, uint64_t blocks, uint64_t m, uint64_t na, uint64_t nb) {
+    CrtScratch s;
+    s.res_bytes = crt_res_bytes(blocks);
+    s.res = (uint8_t*)d.get(Device::S_ZBLK, s.res_bytes);
+    s.ws = d.get(Device::S_LUT3, crt_lut_bytes(std::min(m, crt_max_snps()), na, nb));
+    s.rec = crt_record(d);
+    return s;
+}
+
+// One f64 product K (+)= Za Zb^T over m SNPs, crt_max_snps() per step.  B.P == nullptr: Zb = Za and
+// o is the whole K or a part (a part's residue chunks follow its layout table); else o.k holds the
+// o.blocks dense blocks of the rectangle.  On the CRT path each step is the int8 residue launch
+// (syrk_crt.hip), then the f64 MFMA kernel gated on the step's non-finite flag; off it (hooks "syrk"
+// / "f64") every block runs on the fused f64 MFMA kernel in the same steps.
+static void syrk_f64_steps(Device& d, const PackedSide& A, const PackedSide& B, uint64_t m, const double* lut,
+                           const GrmDest& o, int accumulate) {
     const uint64_t step = crt_max_snps();
-    void* ws = d.get(Device::S_LUT3, crt_lut_bytes(std::min(m, step), n));
-    unsigned long long* rec = crt_record(d);
+    const CrtScratch s = syrk_f64_path() == F64Path::CRT ? crt_scratch(d, o.blocks, m, A.n, B.n) : CrtScratch();
     for (uint64_t s0 = 0; s0 < m; s0 += step) {
         const uint64_t cnt = std::min(step, m - s0);
         const int acc = accumulate || s0 > 0;
-        launch_syrk_packed_crt(packed + s0 * pitch, pitch, n, cnt, lut + 4 * s0, (double*)o.k, acc, ws, res, res_bytes,
-                               rec, d.stream, nullptr, nullptr, o.tab, o.blocks);
-        launch_syrk_packed(packed + s0 * pitch, pitch, n, cnt, lut + 4 * s0, SNPMI_DT_F64, o, acc, d.stream,
-                           (const int*)ws + 1);
+        const PackedSide a{A.P + s0 * A.pitch, A.pitch, A.n}, b{B.P ? B.P + s0 * B.pitch : nullptr, B.pitch, B.n};
+        const double* L = lut + 4 * s0;
+        if (s.ws)
+            launch_syrk_crt(a, b, cnt, L, (double*)o.k, acc, s.ws, s.res, s.res_bytes, s.rec, d.stream, nullptr, nullptr,
+                            o.tab, o.blocks);
+        if (b.P) launch_syrk_rect_f64(a.P, a.pitch, a.n, b.P, b.pitch, b.n, cnt, L, (double*)o.k, acc, d.stream, s.gate());
+        else launch_syrk_packed(a.P, a.pitch, a.n, cnt, L, SNPMI_DT_F64, o, acc, d.stream, s.gate());
     }
 }
 
@@ -814,12 +837,25 @@ static void syrk_packed_mfma(Device& d, const uint8_t* packed, uint64_t pitch, u
     else for_z_blocks(d, packed, pitch, n, m, (const double*)lut, run);
 }
 
-// K (+)= Z Z^T of a packed SNP block into the whole K or one part: the CRT path for f64, else the
-// MFMA paths, for f32 inside the exact diagonal (hook "diag")
+// K (+)= Z Z^T of a packed SNP block into the whole K or one part: f64 in the steps of
+// syrk_f64_steps (the whole K only on the CRT path; a part -- cfg5 in the reference's default dtype --
+// always, its dense launcher being f32 only), else the MFMA paths, for f32 inside the exact diagonal
+// (hook "diag")
 static void syrk_packed_auto(Device& d, const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m,
                              const void* lut, int dt, const GrmDest& o, int accumulate) {
-    if (dt == SNPMI_DT_F64 && syrk_f64_path() == F64Path::CRT && m > 0 && n > 0) {
-        syrk_packed_crt(d, packed, pitch, n, m, (const double*)lut, o, accumulate);
+    const bool part64 = dt == SNPMI_DT_F64 && o.tab;
+    if (part64) {
+        if (o.blocks == 0) return;
+        SNPMI_REQUIRE(4 * o.blocks < (1ull << 31), SNPMI_E_ARG, "too many GRM blocks for one launch");
+        SNPMI_REQUIRE(pitch % 64 == 0 && pitch * 4 >= ceil_div(n, 256) * 256, SNPMI_E_ARG,
+                      "packed pitch must cover round_up(n, 256) iids");
+        if (m == 0) {
+            if (!accumulate) SNPMI_HIP(hipMemsetAsync(o.k, 0, o.blocks * 256 * 256 * sizeof(double), d.stream));
+            return;
+        }
+    }
+    if (part64 || (dt == SNPMI_DT_F64 && syrk_f64_path() == F64Path::CRT && m > 0 && n > 0)) {
+        syrk_f64_steps(d, {packed, pitch, n}, {nullptr, 0, 0}, m, (const double*)lut, o, accumulate);
         return;
     }
     if (dt == SNPMI_DT_F32 && g_diag_exact && m > 0 && n > 0) {
@@ -832,28 +868,6 @@ static void syrk_packed_auto(Device& d, const uint8_t* packed, uint64_t pitch, u
     syrk_packed_mfma(d, packed, pitch, n, m, lut, dt, o, accumulate);
 }
 
-// f64 part (cfg5 in the reference's default dtype): the CRT path over the part's layout; off that
-// path (hooks "syrk" / "f64"), every block on the fused f64 MFMA kernel in the same SNP steps
-static void syrk_packed_part_f64(Device& d, const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m,
-                                 const double* lut, int rank, int world, double* blocks, int accumulate) {
-    const GrmDest o = part_dest(blocks, n, rank, world);
-    if (o.blocks == 0) return;
-    SNPMI_REQUIRE(4 * o.blocks < (1ull << 31), SNPMI_E_ARG, "too many GRM blocks for one launch");
-    SNPMI_REQUIRE(pitch % 64 == 0 && pitch * 4 >= ceil_div(n, 256) * 256, SNPMI_E_ARG,
-                  "packed pitch must cover round_up(n, 256) iids");
-    if (m == 0) {
-        if (!accumulate) SNPMI_HIP(hipMemsetAsync(blocks, 0, o.blocks * 256 * 256 * sizeof(double), d.stream));
-        return;
-    }
-    if (syrk_f64_path() == F64Path::CRT) {
-        syrk_packed_crt(d, packed, pitch, n, m, lut, o, accumulate);
-        return;
-    }
-    const uint64_t step = crt_max_snps();
-    for (uint64_t s0 = 0; s0 < m; s0 += step)
-        launch_syrk_packed(packed + s0 * pitch, pitch, n, std::min(step, m - s0), lut + 4 * s0, SNPMI_DT_F64, o,
-                           accumulate || s0 > 0, d.stream);
-}
 // Finish a GRM held as tiles on the device: optional DiagKtoN, then K (n x n) to the host,
 // extracted in row blocks so the device never needs a second full-size K.
 template <typename T>
@@ -1097,6 +1111,27 @@ static void syrk_dense_auto(Device& d, const void* Z, uint64_t ldz, uint64_t n, 
     launch_syrk_dense(Z, ldz, n, m, dt, tiles, accumulate, d.stream);
 }
 
+// A dense operand (rows = iids, cols = SNPs; F or C order, host or device memory) as the F-order Z
+// of the SYRKs in S_DENSE, *ldz = round_up(rows, 256): the 256-iid panels of the glds SYRK
+template <typename T>
+static T* dense_upload(Device& d, const T* val, uint64_t rows, uint64_t cols, int order_c, uint64_t* ldz) {
+    const uint64_t ld = round_up(std::max<uint64_t>(rows, 1), 256);
+    T* Z = (T*)d.get(Device::S_DENSE, ld * std::max<uint64_t>(cols, 1) * sizeof(T));
+    *ldz = ld;
+    if (cols == 0 || rows == 0) return Z;
+    if (!order_c) {
+        SNPMI_HIP(hipMemcpy2DAsync(Z, ld * sizeof(T), val, rows * sizeof(T), rows * sizeof(T), cols, hipMemcpyDefault,
+                                   d.stream));  // host or device val
+    } else if (is_device_ptr(d, val)) {
+        launch_transpose_to_f(val, rows, cols, DT<T>::v, Z, ld, d.stream);
+    } else {
+        T* Zc = (T*)d.get(Device::S_DENSE2, rows * cols * sizeof(T));
+        SNPMI_HIP(hipMemcpyAsync(Zc, val, rows * cols * sizeof(T), hipMemcpyHostToDevice, d.stream));
+        launch_transpose_to_f(Zc, rows, cols, DT<T>::v, Z, ld, d.stream);
+    }
+    return Z;
+}
+
 template <typename T>
 static void grm_dense_impl(const T* val, uint64_t rows, uint64_t cols, int order_c, int std_kind, double a, double b,
                            int use_stats, T* stats, int diag_k_to_n, double* factor, T* K_out) {
@@ -1104,20 +1139,8 @@ static void grm_dense_impl(const T* val, uint64_t rows, uint64_t cols, int order
     SNPMI_REQUIRE(K_out != nullptr || rows == 0, SNPMI_E_ARG, "K_out is NULL");
     Device& d = device();
     const int dt = DT<T>::v;
-    const uint64_t ldz = round_up(std::max<uint64_t>(rows, 1), 256);  // 256-iid panels of the glds SYRK
-    T* Z = (T*)d.get(Device::S_DENSE, ldz * std::max<uint64_t>(cols, 1) * sizeof(T));
-    if (cols > 0 && rows > 0) {
-        if (!order_c) {
-            SNPMI_HIP(hipMemcpy2DAsync(Z, ldz * sizeof(T), val, rows * sizeof(T), rows * sizeof(T), cols,
-                                       hipMemcpyDefault, d.stream));  // host or device val
-        } else if (is_device_ptr(d, val)) {
-            launch_transpose_to_f(val, rows, cols, dt, Z, ldz, d.stream);
-        } else {
-            T* Zc = (T*)d.get(Device::S_DENSE2, rows * cols * sizeof(T));
-            SNPMI_HIP(hipMemcpyAsync(Zc, val, rows * cols * sizeof(T), hipMemcpyHostToDevice, d.stream));
-            launch_transpose_to_f(Zc, rows, cols, dt, Z, ldz, d.stream);
-        }
-    }
+    uint64_t ldz = 0;
+    T* Z = dense_upload(d, val, rows, cols, order_c, &ldz);
     if (std_kind != SNPMI_STD_NONE && cols > 0) {
         T* ds = (T*)d.get(Device::S_STATS, cols * 2 * sizeof(T));
         if (use_stats) SNPMI_HIP(hipMemcpyAsync(ds, stats, cols * 2 * sizeof(T), hipMemcpyHostToDevice, d.stream));
@@ -1195,47 +1218,38 @@ static void grm_add_dense_impl(const T* val, uint64_t rows, uint64_t cols, int o
     if (rows == 0 || cols == 0) return;
     Device& d = device();
     T* tiles = (T*)session_tiles(d);
-    const uint64_t ldz = round_up(rows, 256);
-    T* Z = (T*)d.get(Device::S_DENSE, ldz * cols * sizeof(T));
-    if (!order_c) {
-        SNPMI_HIP(hipMemcpy2DAsync(Z, ldz * sizeof(T), val, rows * sizeof(T), rows * sizeof(T), cols,
-                                   hipMemcpyDefault, d.stream));  // host or device val
-    } else if (is_device_ptr(d, val)) {
-        launch_transpose_to_f(val, rows, cols, DT<T>::v, Z, ldz, d.stream);
-    } else {
-        T* Zc = (T*)d.get(Device::S_DENSE2, rows * cols * sizeof(T));
-        SNPMI_HIP(hipMemcpyAsync(Zc, val, rows * cols * sizeof(T), hipMemcpyHostToDevice, d.stream));
-        launch_transpose_to_f(Zc, rows, cols, DT<T>::v, Z, ldz, d.stream);
-    }
+    uint64_t ldz = 0;
+    const T* Z = dense_upload(d, val, rows, cols, order_c, &ldz);
     syrk_dense_auto(d, Z, ldz, rows, cols, DT<T>::v, tiles, g_session.wrote ? 1 : 0);
     g_session.wrote = true;
     SNPMI_HIP(hipStreamSynchronize(d.stream));
 }
 
-// Packed SNP columns already in HBM ([m][pitch] bytes, every iid of the session) added to the
-// session: per chunk of <= 2^16 SNPs one stats launch (LUT) and one SYRK launch, so a rank's
-// whole SNP shard accumulates in registers over up to 65536 SNPs per K-tile round trip instead
-// of one per 10k block (the reference's block_size bounds host memory, snpreader.py:651).
-// stats may be host memory (copied synchronously) or device memory (the call then only enqueues).
+// Packed SNP columns already in HBM ([m][pitch] bytes, every iid of the reader): the argument checks
+// every add of them shares, their chunks and the per-chunk stats + LUT.
 template <typename T>
-static void grm_add_packed_impl(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, int count_a1,
-                                int std_kind, double a, double b, int use_stats, T* stats) {
-    std::lock_guard<std::recursive_mutex> lk(g_call_mutex);
-    SNPMI_REQUIRE(g_session.active, SNPMI_E_ARG, "no GRM session (call snpmi_grm_begin)");
-    SNPMI_REQUIRE(g_session.dtype == DT<T>::v, SNPMI_E_ARG, "dtype differs from snpmi_grm_begin");
-    SNPMI_REQUIRE(n == g_session.n, SNPMI_E_ARG, "iid count differs from snpmi_grm_begin");
+static void check_packed_args(uint64_t pitch, uint64_t n, uint64_t m, int std_kind, const T* stats) {
     SNPMI_REQUIRE(pitch % 64 == 0 && pitch >= ceil_div(n, 4), SNPMI_E_ARG, "pitch must be snpmi_packed_pitch");
     SNPMI_REQUIRE(std_kind >= SNPMI_STD_NONE && std_kind <= SNPMI_STD_BETA, SNPMI_E_ARG, "bad standardizer kind");
     SNPMI_REQUIRE(stats != nullptr || std_kind == SNPMI_STD_NONE || m == 0, SNPMI_E_ARG, "stats is NULL");
+}
+// equal chunks of <= 2^16 SNPs (the int32 / CRT accumulation cap), multiples of 256
+static uint64_t packed_chunk_snps(uint64_t m) {
+    const uint64_t nchunk = m ? ceil_div(m, 1ull << 16) : 1;
+    return std::min<uint64_t>(1ull << 16, round_up(ceil_div(m, nchunk), 256));
+}
+// Per chunk one stats launch (LUT) and `mul(src, cnt, lut, last)`, so a rank's whole SNP shard
+// accumulates in registers over up to 65536 SNPs per K-tile round trip instead of one per 10k block
+// (the reference's block_size bounds host memory, snpreader.py:651).  stats may be host memory
+// (copied synchronously) or device memory (the call then only enqueues).
+template <typename T, class Mul>
+static void for_packed_chunks(Device& d, const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, int count_a1,
+                              int std_kind, double a, double b, int use_stats, T* stats, Mul&& mul) {
     if (m == 0 || n == 0) return;
-    SNPMI_REQUIRE(packed != nullptr, SNPMI_E_ARG, "packed is NULL");
-    Device& d = device();
-    SNPMI_REQUIRE(is_device_ptr(d, packed), SNPMI_E_ARG, "packed must be device memory of the current device");
-    T* tiles = (T*)session_tiles(d);
+    SNPMI_REQUIRE(packed != nullptr && is_device_ptr(d, packed), SNPMI_E_ARG,
+                  "packed must be device memory of the current device");
     const bool host_stats = stats && std_kind != SNPMI_STD_NONE && !is_device_ptr(d, stats);
-    // equal chunks of <= 2^16 SNPs (the int32 / CRT accumulation cap), multiples of 256
-    const uint64_t nchunk = ceil_div(m, 1ull << 16);
-    const uint64_t step = std::min<uint64_t>(1ull << 16, round_up(ceil_div(m, nchunk), 256));
+    const uint64_t step = packed_chunk_snps(m);
     for (uint64_t s0 = 0; s0 < m; s0 += step) {
         const uint64_t cnt = std::min(step, m - s0);
         const uint8_t* src = packed + s0 * pitch;
@@ -1244,14 +1258,43 @@ static void grm_add_packed_impl(const uint8_t* packed, uint64_t pitch, uint64_t 
         if (host_stats && use_stats)
             SNPMI_HIP(hipMemcpyAsync(st, stats + 2 * s0, cnt * 2 * sizeof(T), hipMemcpyHostToDevice, d.stream));
         launch_snp_stats(src, pitch, n, cnt, count_a1, std_kind, a, b, use_stats, DT<T>::v, st, lut, d.stream);
-        syrk_packed_auto(d, src, pitch, n, cnt, lut, DT<T>::v, whole_dest(tiles, n), g_session.wrote ? 1 : 0);
-        g_session.wrote = true;
+        mul(src, cnt, (const T*)lut, s0 + cnt == m);
         if (host_stats && !use_stats) {
             SNPMI_HIP(hipMemcpyAsync(stats + 2 * s0, st, cnt * 2 * sizeof(T), hipMemcpyDeviceToHost, d.stream));
             SNPMI_HIP(hipStreamSynchronize(d.stream));  // S_STATS is reused by the next chunk
         }
     }
     if (host_stats) SNPMI_HIP(hipStreamSynchronize(d.stream));
+}
+
+template <typename T>
+static void check_session_packed(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, int std_kind,
+                                 const T* stats) {
+    SNPMI_REQUIRE(g_session.active, SNPMI_E_ARG, "no GRM session (call snpmi_grm_begin)");
+    SNPMI_REQUIRE(g_session.dtype == DT<T>::v, SNPMI_E_ARG, "dtype differs from snpmi_grm_begin");
+    SNPMI_REQUIRE(n == g_session.n, SNPMI_E_ARG, "iid count differs from snpmi_grm_begin");
+    check_packed_args(pitch, n, m, std_kind, stats);
+    SNPMI_REQUIRE(packed != nullptr || m == 0 || n == 0, SNPMI_E_ARG, "packed is NULL");
+}
+// one chunk into the session's tiles
+template <typename T>
+static void session_add_chunk(Device& d, const uint8_t* src, uint64_t pitch, uint64_t cnt, const T* lut) {
+    syrk_packed_auto(d, src, pitch, g_session.n, cnt, lut, DT<T>::v, whole_dest(session_tiles(d), g_session.n),
+                     g_session.wrote ? 1 : 0);
+    g_session.wrote = true;
+}
+
+// the chunks added to the session
+template <typename T>
+static void grm_add_packed_impl(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, int count_a1,
+                                int std_kind, double a, double b, int use_stats, T* stats) {
+    std::lock_guard<std::recursive_mutex> lk(g_call_mutex);
+    check_session_packed(packed, pitch, n, m, std_kind, stats);
+    Device& d = device();
+    for_packed_chunks(d, packed, pitch, n, m, count_a1, std_kind, a, b, use_stats, stats,
+                      [&](const uint8_t* src, uint64_t cnt, const T* lut, bool) {
+                          session_add_chunk(d, src, pitch, cnt, lut);
+                      });
 }
 // Column groups of the upper triangle for an overlapped collective: ranges [L0, L1) of 256-block
 // indices covering whole supertile columns (16 block columns).  The last group holds ~1/4 of the
@@ -1350,11 +1393,6 @@ static bool f32_groupable(Device& d, uint64_t n, int parts) {
            bf3_split_slices(n, 1ull << 16, d.cu_count) == 1 && ceil_div(n, 256) < 65536;
 }
 
-static uint64_t crt_res_bytes(uint64_t n) {
-    const uint64_t nb = ceil_div(n, 256);
-    return std::min<uint64_t>(nb * (nb + 1) / 2 * (uint64_t)crt_moduli() * 65536, 4ull << 30);
-}
-
 // The K-tile collective of one session as RCCL calls: 128-tile column ranges [t0, t1) of the
 // triangle, each one in-place sum.  f32: the column groups of the overlapped SYRK; f64 on the CRT
 // path: its column-aligned residue chunks; otherwise one range over the whole triangle.  Every path
@@ -1370,7 +1408,8 @@ static SumPlan sum_plan(Device& d, uint64_t n, int dtype, int parts) {
         for (const auto& g : column_groups(ceil_div(n, 256), parts)) p.ranges.push_back({2 * g.c0, 2 * g.c1});
         p.grouped = true;
     } else if (dtype == SNPMI_DT_F64 && syrk_f64_path() == F64Path::CRT && n > 0) {
-        for (const auto& c : crt_column_chunks(n, crt_res_bytes(n))) p.ranges.push_back({2 * c.first, 2 * c.second});
+        for (const auto& c : crt_column_chunks(n, crt_res_bytes(whole_dest(nullptr, n).blocks)))
+            p.ranges.push_back({2 * c.first, 2 * c.second});
         p.grouped = true;
     } else {
         p.ranges.push_back({0, n_tiles_1d(n)});
@@ -1412,7 +1451,7 @@ static int grouped_reduce_f32(Device& d, const uint8_t* src, uint64_t pitch, uin
 }
 
 // f64 counterpart: the groups are the CRT path's residue chunks of the last <= crt_max_snps() SNPs
-// (launch_syrk_packed_crt cuts them at block-column boundaries when given after_chunk; ~5 at 50k
+// (launch_syrk_crt cuts them at block-column boundaries when given after_chunk; ~5 at 50k
 // iids, so no extra launch boundary), each chunk's f64 tiles summed on the aux stream once its
 // CRT reconstruction is done.  The f64-MFMA fallback of a non-finite LUT (gated on the device
 // flag) runs before the chunks, so every sum sees final tiles.
@@ -1422,21 +1461,18 @@ static int crt_reduce_f64(Device& d, const uint8_t* src, uint64_t pitch, uint64_
     const GrmDest o = whole_dest(tiles, n);
     if (cnt > step) {  // the leading SNPs the plain way, the last <= step overlapped
         const uint64_t lead = ((cnt - 1) / step) * step;
-        syrk_packed_crt(d, src, pitch, n, lead, lut, o, acc);
+        syrk_f64_steps(d, {src, pitch, n}, {nullptr, 0, 0}, lead, lut, o, acc);
         src += lead * pitch;
         lut += 4 * lead;
         cnt -= lead;
         acc = 1;
     }
-    const uint64_t res_bytes = crt_res_bytes(n);
-    uint8_t* res = (uint8_t*)d.get(Device::S_ZBLK, res_bytes);
-    void* ws = d.get(Device::S_LUT3, crt_lut_bytes(cnt, n));
-    unsigned long long* rec = crt_record(d);
+    const CrtScratch s = crt_scratch(d, o.blocks, cnt, n, 0);
     const SumPlan plan = sum_plan(d, n, SNPMI_DT_F64, 1);
     OverlapSums sums(d, collective, rt, SNPMI_DT_F64);
     size_t groups = 0;
     const std::function<void()> pre = [&] {
-        launch_syrk_packed(src, pitch, n, cnt, lut, SNPMI_DT_F64, o, acc, d.stream, (const int*)ws + 1);
+        launch_syrk_packed(src, pitch, n, cnt, lut, SNPMI_DT_F64, o, acc, d.stream, s.gate());
     };
     const std::function<void(uint64_t, uint64_t)> after = [&](uint64_t c0, uint64_t c1) {
         SNPMI_REQUIRE(groups < plan.ranges.size() && plan.ranges[groups] == std::make_pair(2 * c0, 2 * c1),
@@ -1444,7 +1480,8 @@ static int crt_reduce_f64(Device& d, const uint8_t* src, uint64_t pitch, uint64_
         groups++;
         sums.range(tiles, n, 2 * c0, 2 * c1);
     };
-    launch_syrk_packed_crt(src, pitch, n, cnt, lut, tiles, acc, ws, res, res_bytes, rec, d.stream, &pre, &after);
+    launch_syrk_crt({src, pitch, n}, {nullptr, 0, 0}, cnt, lut, tiles, acc, s.ws, s.res, s.res_bytes, s.rec, d.stream,
+                    &pre, &after);
     SNPMI_REQUIRE(groups == plan.ranges.size(), SNPMI_E_ARG, "CRT chunks differ from the collective plan");
     if (syrk_done) SNPMI_HIP(hipEventRecord(syrk_done, d.stream));
     sums.join();
@@ -1475,7 +1512,7 @@ static void check_reduce_args(int collective, int parts) {
 }
 
 // snpmi_grm_add_packed_{f32,f64} (the session's last add) + the K-tile collective, overlapped:
-// the last SNP chunk (same chunking as grm_add_packed_impl) runs through grouped_reduce_f32 /
+// the last SNP chunk of for_packed_chunks runs through grouped_reduce_f32 /
 // crt_reduce_f64.  Host stats, or a path without groups, add first and sum after.
 template <typename T>
 static void grm_add_packed_reduce_impl(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, int count_a1,
@@ -1485,8 +1522,6 @@ static void grm_add_packed_reduce_impl(const uint8_t* packed, uint64_t pitch, ui
     check_reduce_args<T>(collective, parts);
     Device& d = device();
     const int rt = collective == 1 ? root : -1;
-    const uint64_t nchunk = m ? ceil_div(m, 1ull << 16) : 1;
-    const uint64_t step = std::min<uint64_t>(1ull << 16, round_up(ceil_div(m, nchunk), 256));
     const bool grouped = m > 0 && n > 0 && n == g_session.n && sum_plan(d, n, DT<T>::v, parts).grouped &&
                          (std_kind == SNPMI_STD_NONE || (stats && is_device_ptr(d, stats)));
     g_last_groups = 1;
@@ -1495,24 +1530,20 @@ static void grm_add_packed_reduce_impl(const uint8_t* packed, uint64_t pitch, ui
         session_sum_planned<T>(d, collective, rt, parts, syrk_done);
         return;
     }
-    SNPMI_REQUIRE(pitch % 64 == 0 && pitch >= ceil_div(n, 4), SNPMI_E_ARG, "pitch must be snpmi_packed_pitch");
-    SNPMI_REQUIRE(std_kind >= SNPMI_STD_NONE && std_kind <= SNPMI_STD_BETA, SNPMI_E_ARG, "bad standardizer kind");
-    SNPMI_REQUIRE(packed != nullptr && is_device_ptr(d, packed), SNPMI_E_ARG,
-                  "packed must be device memory of the current device");
-    const uint64_t s_last = ((m - 1) / step) * step;
-    if (s_last > 0) grm_add_packed_impl<T>(packed, pitch, n, s_last, count_a1, std_kind, a, b, use_stats, stats);
-    T* tiles = (T*)session_tiles(d);
-    const int acc = g_session.wrote ? 1 : 0;
-    const uint64_t cnt = m - s_last;
-    const uint8_t* src = packed + s_last * pitch;
-    T* lut = (T*)d.get(Device::S_LUT, cnt * 4 * sizeof(T));
-    launch_snp_stats(src, pitch, n, cnt, count_a1, std_kind, a, b, use_stats, DT<T>::v,
-                     stats ? stats + 2 * s_last : (T*)d.get(Device::S_STATS, cnt * 2 * sizeof(T)), lut, d.stream);
-    g_session.wrote = true;
-    if constexpr (std::is_same<T, double>::value)
-        g_last_groups = crt_reduce_f64(d, src, pitch, n, cnt, lut, tiles, acc, collective, rt, syrk_done);
-    else
-        g_last_groups = grouped_reduce_f32(d, src, pitch, n, cnt, lut, tiles, acc, collective, rt, parts, syrk_done);
+    check_packed_args(pitch, n, m, std_kind, stats);
+    for_packed_chunks(d, packed, pitch, n, m, count_a1, std_kind, a, b, use_stats, stats,
+                      [&](const uint8_t* src, uint64_t cnt, const T* lut, bool last) {
+                          if (!last) return session_add_chunk(d, src, pitch, cnt, lut);
+                          T* tiles = (T*)session_tiles(d);
+                          const int acc = g_session.wrote ? 1 : 0;
+                          g_session.wrote = true;
+                          if constexpr (std::is_same<T, double>::value)
+                              g_last_groups = crt_reduce_f64(d, src, pitch, n, cnt, lut, tiles, acc, collective, rt,
+                                                             syrk_done);
+                          else
+                              g_last_groups = grouped_reduce_f32(d, src, pitch, n, cnt, lut, tiles, acc, collective, rt,
+                                                                 parts, syrk_done);
+                      });
 }
 
 // snpmi_grm_add_bed_{f32,f64} (the session's last add: a rank's SNP span of a .bed) + the K-tile
@@ -1649,8 +1680,8 @@ static RectPairs rect_pairs_upload(Device& d, const uint32_t* host_pairs, uint64
     return p;
 }
 
-// blocks (+)= Za Zb^T of one SNP block: f64 on the CRT path in crt_max_snps() steps (the f64 MFMA
-// kernel gated on its non-finite flag), f32 on the fp16x2 / bf16x3 chain with the exact diagonal
+// blocks (+)= Za Zb^T of one SNP block: f64 in the steps of syrk_f64_steps, f32 on the fp16x2 /
+// bf16x3 chain with the exact diagonal
 // of the matched positions (hook "diag"), as syrk_packed_auto does for the whole K
 static void syrk_rect_auto(Device& d, const uint8_t* Pa, uint64_t pitch_a, uint64_t na, const uint8_t* Pb,
                            uint64_t pitch_b, uint64_t nb, uint64_t m, const void* lut, int dt, void* blocks,
@@ -1662,22 +1693,8 @@ static void syrk_rect_auto(Device& d, const uint8_t* Pa, uint64_t pitch_a, uint6
         return;
     }
     if (dt == SNPMI_DT_F64) {
-        const double* L = (const double*)lut;
-        const bool crt = syrk_f64_path() == F64Path::CRT;
-        const uint64_t step = crt_max_snps();
-        const uint64_t res_bytes = std::min<uint64_t>(g * (uint64_t)crt_moduli() * 65536, 4ull << 30);
-        uint8_t* res = crt ? (uint8_t*)d.get(Device::S_ZBLK, res_bytes) : nullptr;
-        void* ws = crt ? d.get(Device::S_LUT3, crt_rect_lut_bytes(std::min(m, step), na, nb)) : nullptr;
-        unsigned long long* rec = crt ? crt_record(d) : nullptr;
-        for (uint64_t s0 = 0; s0 < m; s0 += step) {
-            const uint64_t cnt = std::min(step, m - s0);
-            const int acc = accumulate || s0 > 0;
-            if (crt)
-                launch_syrk_rect_crt(Pa + s0 * pitch_a, pitch_a, na, Pb + s0 * pitch_b, pitch_b, nb, cnt, L + 4 * s0,
-                                     (double*)blocks, acc, ws, res, res_bytes, rec, d.stream);
-            launch_syrk_rect_f64(Pa + s0 * pitch_a, pitch_a, na, Pb + s0 * pitch_b, pitch_b, nb, cnt, L + 4 * s0,
-                                 (double*)blocks, acc, d.stream, crt ? (const int*)ws + 1 : nullptr);
-        }
+        syrk_f64_steps(d, {Pa, pitch_a, na}, {Pb, pitch_b, nb}, m, (const double*)lut, {blocks, nullptr, nullptr, g},
+                       accumulate);
         return;
     }
     H2Lut h2;
@@ -1772,33 +1789,15 @@ static void rect_add_packed_impl(const uint8_t* packed, uint64_t pitch, uint64_t
                                  const uint64_t* col_idx) {
     std::lock_guard<std::recursive_mutex> lk(g_call_mutex);
     rect_check_session<T>(n, row_idx, col_idx);
-    SNPMI_REQUIRE(pitch % 64 == 0 && pitch >= ceil_div(n, 4), SNPMI_E_ARG, "pitch must be snpmi_packed_pitch");
-    SNPMI_REQUIRE(std_kind >= SNPMI_STD_NONE && std_kind <= SNPMI_STD_BETA, SNPMI_E_ARG, "bad standardizer kind");
-    SNPMI_REQUIRE(stats != nullptr || std_kind == SNPMI_STD_NONE || m == 0, SNPMI_E_ARG, "stats is NULL");
+    check_packed_args(pitch, n, m, std_kind, stats);
     Device& d = device();
     const RectAdd ra = rect_add_begin<T>(d, n, row_idx, col_idx);
-    if (m == 0 || n == 0) return;
-    SNPMI_REQUIRE(packed != nullptr && is_device_ptr(d, packed), SNPMI_E_ARG,
-                  "packed must be device memory of the current device");
-    const bool host_stats = stats && std_kind != SNPMI_STD_NONE && !is_device_ptr(d, stats);
     // the chunks of snpmi_grm_add_packed_*: the same launch boundaries as the whole-K session
-    const uint64_t nchunk = ceil_div(m, 1ull << 16);
-    const uint64_t step = std::min<uint64_t>(1ull << 16, round_up(ceil_div(m, nchunk), 256));
-    for (uint64_t s0 = 0; s0 < m; s0 += step) {
-        const uint64_t cnt = std::min(step, m - s0);
-        const uint8_t* src = packed + s0 * pitch;
-        T* lut = (T*)d.get(Device::S_LUT, cnt * 4 * sizeof(T));
-        T* st = (stats && !host_stats) ? stats + 2 * s0 : (T*)d.get(Device::S_STATS, cnt * 2 * sizeof(T));
-        if (host_stats && use_stats)
-            SNPMI_HIP(hipMemcpyAsync(st, stats + 2 * s0, cnt * 2 * sizeof(T), hipMemcpyHostToDevice, d.stream));
-        launch_snp_stats(src, pitch, n, cnt, count_a1, std_kind, a, b, use_stats, DT<T>::v, st, lut, d.stream);
-        rect_add_chunk<T>(d, ra, src, pitch, cnt, lut);
-        if (host_stats && !use_stats) {
-            SNPMI_HIP(hipMemcpyAsync(stats + 2 * s0, st, cnt * 2 * sizeof(T), hipMemcpyDeviceToHost, d.stream));
-            SNPMI_HIP(hipStreamSynchronize(d.stream));  // S_STATS is reused by the next chunk
-        }
-    }
-    SNPMI_HIP(hipStreamSynchronize(d.stream));
+    for_packed_chunks(d, packed, pitch, n, m, count_a1, std_kind, a, b, use_stats, stats,
+                      [&](const uint8_t* src, uint64_t cnt, const T* lut, bool) {
+                          rect_add_chunk<T>(d, ra, src, pitch, cnt, lut);
+                      });
+    if (m > 0 && n > 0) SNPMI_HIP(hipStreamSynchronize(d.stream));
 }
 
 template <typename T>
@@ -2756,11 +2755,7 @@ static void grm_part_bed_impl(const char* path, uint64_t n_iid, uint64_t n_sid, 
         d, true, path, n_iid, n_sid, count_a1, iid_idx, n_out_iid, sid_idx, n_out_sid, std_kind, a, b, use_stats,
         stats, num_threads,
         [&](const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t cnt, const T* lut, bool acc) {
-            if constexpr (std::is_same<T, double>::value)
-                syrk_packed_part_f64(d, packed, pitch, n, cnt, lut, part_rank, part_world, blocks, acc);
-            else
-                syrk_packed_auto(d, packed, pitch, n, cnt, lut, SNPMI_DT_F32,
-                                 part_dest(blocks, n, part_rank, part_world), acc);
+            syrk_packed_auto(d, packed, pitch, n, cnt, lut, DT<T>::v, part_dest(blocks, n, part_rank, part_world), acc);
         });
     if (!wrote) SNPMI_HIP(hipMemsetAsync(blocks, 0, dev_out ? nloc * 256 * 256 * sizeof(T) : bytes, d.stream));
     const size_t bb = 256 * 256 * sizeof(T);  // one block per "row" of the pinned-bounce copy
@@ -2892,7 +2887,8 @@ int snpmi_dev_syrk_packed_part_f64(const uint8_t* packed, uint64_t pitch, uint64
         std::lock_guard<std::recursive_mutex> lk(g_call_mutex);  // shared scratch slots
         SNPMI_REQUIRE(part_world >= 1 && part_rank >= 0 && part_rank < part_world, SNPMI_E_ARG, "bad partition");
         SNPMI_REQUIRE(pitch % 64 == 0 && pitch >= ceil_div(n_iid, 4), SNPMI_E_ARG, "pitch must be snpmi_packed_pitch");
-        syrk_packed_part_f64(device(), packed, pitch, n_iid, n_sid, lut, part_rank, part_world, blocks, accumulate);
+        syrk_packed_auto(device(), packed, pitch, n_iid, n_sid, lut, SNPMI_DT_F64,
+                         part_dest(blocks, n_iid, part_rank, part_world), accumulate);
     });
 }
 

@@ -286,12 +286,7 @@ void launch_syrk_rect_f32(const uint8_t* Pa, uint64_t pitch_a, uint64_t n_a, con
 void launch_syrk_rect_f64(const uint8_t* Pa, uint64_t pitch_a, uint64_t n_a, const uint8_t* Pb, uint64_t pitch_b,
                           uint64_t n_b, uint64_t m, const double* lut, double* blocks, int accumulate, hipStream_t st,
                           const int* gate = nullptr);
-// the CRT form: ws_lut = crt_rect_lut_bytes(m, n_a, n_b); one bound table per operand, block (bi, bj)
-// runs the moduli with P_R > 2 sqrt(M_bi(A) M_bj(B))
-uint64_t crt_rect_lut_bytes(uint64_t m, uint64_t n_a, uint64_t n_b);
-void launch_syrk_rect_crt(const uint8_t* Pa, uint64_t pitch_a, uint64_t n_a, const uint8_t* Pb, uint64_t pitch_b,
-                          uint64_t n_b, uint64_t m, const double* lut, double* blocks, int accumulate, void* ws_lut,
-                          uint8_t* res, uint64_t res_bytes, unsigned long long* rec, hipStream_t st);
+// (the CRT form is launch_syrk_crt with a second operand, below)
 // rect blocks -> the outer range [o0, o0 + no) of K_out's slow axis (rows if order_c, else columns;
 // `inner` = the fast axis' length), contiguous, times scale (rect.hip)
 void launch_rect_extract(const void* blocks, int dtype, uint64_t nba, uint64_t inner, uint64_t o0, uint64_t no,
@@ -342,29 +337,35 @@ void launch_syrk_packed_bf3_split(const uint8_t* packed, uint64_t pitch, uint64_
 void launch_tile_reduce(const float* partial, unsigned slices, uint64_t elems, float* tiles, int accumulate,
                         hipStream_t st);
 // f64 GRM of packed SNPs on the int8 MFMA pipe (syrk_crt.hip): residues modulo crt_moduli()
-// moduli, CRT back to f64.  ws_lut = crt_lut_bytes(m, n) of scratch (its first ints: block
-// exponent, the non-finite flag, the moduli count R this block needs), res = residue scratch
-// (>= crt_moduli() * 64 KiB; more = fewer launches); m <= crt_max_snps(); rec (device, may be
-// NULL): rec[0] += R, rec[1] += 1 per launch
+// moduli, CRT back to f64, out (+)= Za Zb^T.  One operand (B.P == nullptr, Zb = Za): out = the
+// upper-triangle tiles of K, or with part_tab (cfg5) the part's part_blocks dense 256x256 f64
+// blocks in the order of its layout table (PartTables::tab).  Two operands: the rect blocks, one
+// bound table per operand, block (bi, bj) runs the moduli with P_R > 2 sqrt(M_bi(A) M_bj(B)).
+// ws_lut = crt_lut_bytes(m, A.n, B.n) of scratch, laid out in one place (syrk_crt.hip CrtWs: ctl |
+// residue LUT | bound table | bound sums | panel bounds; ctl's first ints are the block exponent,
+// the non-finite flag, the launch-wide moduli count R); res = residue scratch (>= crt_moduli() *
+// 64 KiB; more = fewer launches); m <= crt_max_snps(); rec (device, may be NULL): rec[0] += R,
+// rec[1] += 1 per launch.
+struct PackedSide {
+    const uint8_t* P;  // codes [m][pitch]
+    uint64_t pitch, n;
+};
 int crt_moduli();
 extern int g_crt_kernel;  // residue SYRK form (hook "crt"): 0 = k_syrk_i8r, 1 = warp-specialised k_syrk_i8w
 extern int g_crt_block;   // hook "crt_block": 1 = moduli per 256-block (default), 0 = launch-wide R
 uint64_t crt_max_snps();
-uint64_t crt_lut_bytes(uint64_t m, uint64_t n);
+uint64_t crt_lut_bytes(uint64_t m, uint64_t n_a, uint64_t n_b = 0);
 int crt_fraction_bits(uint64_t m);
 // block columns [c0, c1) of each residue chunk of the overlapped form (after_chunk below)
 std::vector<std::pair<uint64_t, uint64_t>> crt_column_chunks(uint64_t n, uint64_t res_bytes);
-// before_chunks (optional) is enqueued after the per-launch bound/moduli kernels and before the
-// first residue chunk; after_chunk(c0, c1) (optional) after the chunk whose blocks are the whole
-// block columns [c0, c1) (chunks are then cut at column boundaries, so each one's tiles are one
-// contiguous range): the overlapped collective of api.hip grm_add_packed_reduce.
-void launch_syrk_packed_crt(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, const double* lut,
-                            double* tiles, int accumulate, void* ws_lut, uint8_t* res, uint64_t res_bytes,
-                            unsigned long long* rec, hipStream_t st,
-                            const std::function<void()>* before_chunks = nullptr,
-                            const std::function<void(uint64_t, uint64_t)>* after_chunk = nullptr,
-                            const uint32_t* part_tab = nullptr, uint64_t part_blocks = 0);
-// part_tab (cfg5): tiles = the part's part_blocks dense 256x256 f64 blocks in the order of its
-// layout table (PartTables::tab); no after_chunk.
+// before_chunks (optional) is enqueued after the per-launch table / bound / moduli / panel kernels
+// and before the first residue chunk; after_chunk(c0, c1) (optional, whole K only) after the chunk
+// whose blocks are the whole block columns [c0, c1) (chunks are then cut at column boundaries, so
+// each one's tiles are one contiguous range): the overlapped collective of api.hip crt_reduce_f64.
+void launch_syrk_crt(const PackedSide& A, const PackedSide& B, uint64_t m, const double* lut, double* out,
+                     int accumulate, void* ws_lut, uint8_t* res, uint64_t res_bytes, unsigned long long* rec,
+                     hipStream_t st, const std::function<void()>* before_chunks = nullptr,
+                     const std::function<void(uint64_t, uint64_t)>* after_chunk = nullptr,
+                     const uint32_t* part_tab = nullptr, uint64_t part_blocks = 0);
 
 }  // namespace snpmi

@@ -724,13 +724,36 @@ int g_crt_block = 1;
 uint64_t crt_max_snps() { return 1ull << 16; }  // keeps F >= 50 and the int32 sums exact
 int crt_moduli() { return kR; }
 
-// ctl (256 B) | residue LUT (kR x mpad u32) | bound table (4 x mpad f64) | per-iid bound sums (n f64) |
-// per-panel log2 bounds (ceil(n / 256) f64)
-uint64_t crt_lut_bytes(uint64_t m, uint64_t n) {
-    const uint64_t mpad = round_up(std::max<uint64_t>(m, 1), SK);
-    return 256 + (uint64_t)kR * mpad * 4 + mpad * 32 + round_up(std::max<uint64_t>(n, 1), 2) * 8 +
-           round_up(ceil_div(std::max<uint64_t>(n, 1), BW), 2) * 8;
+// The workspace of one CRT launch, for one operand (n_b = 0) or two:
+//   ctl (256 B) | residue LUT (kR x mpad u32) | bound table (4 x mpad f64) |
+//   per-iid bound sums of A, then B | per-panel log2 bounds (one per 256 iids) of A, then B
+// every f64 array an even count, 32 B spare at the end.  base == nullptr: only `bytes` is meaningful.
+struct CrtWs {
+    int* ctl;
+    uint32_t* lutr;
+    double *qsq, *Sa, *Sb, *lga, *lgb;
+    uint64_t mpad, bytes;
+};
+static CrtWs crt_ws(void* base, uint64_t m, uint64_t n_a, uint64_t n_b) {
+    CrtWs w;
+    w.mpad = round_up(std::max<uint64_t>(m, 1), SK);
+    uint64_t off = 0;
+    auto take = [&](uint64_t bytes) {
+        void* p = base ? (uint8_t*)base + off : nullptr;
+        off += bytes;
+        return p;
+    };
+    w.ctl = (int*)take(256);
+    w.lutr = (uint32_t*)take((uint64_t)kR * w.mpad * 4);
+    w.qsq = (double*)take(w.mpad * 32);
+    w.Sa = (double*)take(round_up(n_a, 2) * 8);
+    w.Sb = (double*)take(round_up(n_b, 2) * 8);
+    w.lga = (double*)take(round_up(ceil_div(n_a, BW), 2) * 8);
+    w.lgb = (double*)take(round_up(ceil_div(n_b, BW), 2) * 8);
+    w.bytes = off + 32;
+    return w;
 }
+uint64_t crt_lut_bytes(uint64_t m, uint64_t n_a, uint64_t n_b) { return crt_ws(nullptr, m, n_a, n_b).bytes; }
 
 static CrtLog crt_logs() {
     CrtLog L{};
@@ -739,7 +762,34 @@ static CrtLog crt_logs() {
     return L;
 }
 
-// The residue chunks of launch_syrk_packed_crt's overlapped form as block columns [c0, c1): each
+// What every CRT launch enqueues before its residue chunks: block exponent and residue LUT + bound
+// table of the m SNPs, then per operand (B.P == nullptr: one operand) the per-iid bound sums, the
+// moduli count (k_crt_r scans A's sums and, behind their even padding, B's: the launch-wide R of
+// hook "crt_block" = 0 comes from the larger of the two maxima, sqrt(Ma Mb) <= max(Ma, Mb)) and the
+// per-panel bounds.
+static CrtLog crt_prologue(const CrtWs& w, const PackedSide& A, const PackedSide& B, uint64_t m, const double* lut, int F,
+                           unsigned long long* rec, hipStream_t st) {
+    k_crt_exp<<<1, 1024, 0, st>>>(lut, 4 * m, w.ctl);
+    k_crt_lut<<<(unsigned)ceil_div(w.mpad, 256), 256, 0, st>>>(lut, m, w.mpad, F, w.ctl, w.lutr, w.qsq);
+    const uint64_t zero = B.P ? round_up(A.n, 2) + round_up(B.n, 2) : A.n;
+    const uint64_t scan = B.P ? round_up(A.n, 2) + B.n : A.n;
+    SNPMI_HIP(hipMemsetAsync(w.Sa, 0, zero * sizeof(double), st));
+    auto bound = [&](const PackedSide& s, double* S) {
+        k_crt_bound<<<dim3((unsigned)ceil_div(ceil_div(s.n, 16), 256), (unsigned)ceil_div(m, kBoundSlice)), 256, 0, st>>>(
+            s.P, s.pitch, s.n, m, w.qsq, w.ctl, S);
+    };
+    bound(A, w.Sa);
+    if (B.P) bound(B, w.Sb);
+    static const CrtLog logs0 = crt_logs();
+    CrtLog logs = logs0;
+    logs.per_block = g_crt_block;
+    k_crt_r<<<1, 1024, 0, st>>>(w.Sa, scan, logs, w.ctl, rec);
+    k_crt_panels<<<(unsigned)ceil_div(A.n, BW), 256, 0, st>>>(w.Sa, A.n, w.ctl, w.lga);
+    if (B.P) k_crt_panels<<<(unsigned)ceil_div(B.n, BW), 256, 0, st>>>(w.Sb, B.n, w.ctl, w.lgb);
+    return logs;
+}
+
+// The residue chunks of launch_syrk_crt's overlapped form as block columns [c0, c1): each
 // chunk holds as many whole block columns as `res_bytes` of residues allow (at least one; block
 // column c ends at block (c+1)(c+2)/2).  A function of n and res_bytes only, so every rank of an
 // overlapped collective cuts the same chunks (api.hip sum_plan).
@@ -759,40 +809,30 @@ std::vector<std::pair<uint64_t, uint64_t>> crt_column_chunks(uint64_t n, uint64_
     return out;
 }
 
-// K_tiles (+)= Z Z^T for packed codes + f64 LUT; ws_lut: crt_lut_bytes(m); res: res_bytes of
-// scratch (>= kR * 65536); gate: device u32 set when the block must run on the f64 MFMA instead
-void launch_syrk_packed_crt(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, const double* lut,
-                            double* tiles, int accumulate, void* ws_lut, uint8_t* res, uint64_t res_bytes,
-                            unsigned long long* rec, hipStream_t st, const std::function<void()>* before_chunks,
-                            const std::function<void(uint64_t, uint64_t)>* after_chunk, const uint32_t* part_tab,
-                            uint64_t part_blocks) {
+// out (+)= Za Zb^T for packed codes + f64 LUT.  B.P == nullptr: Zb = Za, out = the upper-triangle
+// tiles of K or (part_tab) a part's dense blocks; else the dense 256 x 256 blocks of the rectangle
+// (slot bj * nba + bi).  ws_lut: crt_lut_bytes(m, A.n, B.n); res: res_bytes of scratch (>= kR * 65536)
+void launch_syrk_crt(const PackedSide& A, const PackedSide& B, uint64_t m, const double* lut, double* out,
+                     int accumulate, void* ws_lut, uint8_t* res, uint64_t res_bytes, unsigned long long* rec,
+                     hipStream_t st, const std::function<void()>* before_chunks,
+                     const std::function<void(uint64_t, uint64_t)>* after_chunk, const uint32_t* part_tab,
+                     uint64_t part_blocks) {
     SNPMI_REQUIRE(m > 0 && m <= crt_max_snps(), SNPMI_E_ARG, "crt SYRK: SNP count per launch out of range");
-    SNPMI_REQUIRE(!part_tab || !after_chunk, SNPMI_E_ARG, "crt SYRK: column chunks of a part");
-    const uint64_t nb = ceil_div(n, BW), total = part_tab ? part_blocks : nb * (nb + 1) / 2;
+    SNPMI_REQUIRE(!(part_tab || B.P) || !after_chunk, SNPMI_E_ARG, "crt SYRK: column chunks of a part");
+    const uint64_t nb = ceil_div(A.n, BW);
+    const uint64_t total = B.P ? rect_blocks(A.n, A.pitch, B.n, B.pitch) : part_tab ? part_blocks : nb * (nb + 1) / 2;
     if (total == 0) return;
-    const uint64_t mpad = round_up(m, SK);
-    int* ctl = (int*)ws_lut;
-    uint32_t* lutr = (uint32_t*)((uint8_t*)ws_lut + 256);
-    double* qsq = (double*)(lutr + (uint64_t)kR * mpad);
-    double* S = qsq + 4 * mpad;
-    double* lgp = S + round_up(std::max<uint64_t>(n, 1), 2);
+    const CrtWs w = crt_ws(ws_lut, m, A.n, B.n);
     const int F = crt_fraction_bits(m);
-    k_crt_exp<<<1, 1024, 0, st>>>(lut, 4 * m, ctl);
-    k_crt_lut<<<(unsigned)ceil_div(mpad, 256), 256, 0, st>>>(lut, m, mpad, F, ctl, lutr, qsq);
-    SNPMI_HIP(hipMemsetAsync(S, 0, n * sizeof(double), st));
-    k_crt_bound<<<dim3((unsigned)ceil_div(ceil_div(n, 16), 256), (unsigned)ceil_div(m, kBoundSlice)), 256, 0, st>>>(
-        packed, pitch, n, m, qsq, ctl, S);
-    static const CrtLog logs0 = crt_logs();
-    CrtLog logs = logs0;
-    logs.per_block = g_crt_block;
-    k_crt_r<<<1, 1024, 0, st>>>(S, n, logs, ctl, rec);
-    k_crt_panels<<<(unsigned)nb, 256, 0, st>>>(S, n, ctl, lgp);
-    const uint64_t per = std::max<uint64_t>(1, res_bytes / ((uint64_t)kR * BW * BW));
+    const CrtLog logs = crt_prologue(w, A, B, m, lut, F, rec, st);
+    uint64_t per = std::max<uint64_t>(1, res_bytes / ((uint64_t)kR * BW * BW));
+    if (B.P) per = std::min<uint64_t>(per, (1ull << 23) - 8);
     static const CrtConst cc = crt_constants();
+    const RectArg<true> rb{B.P, B.pitch, (uint32_t)nb, w.lgb};
     if (before_chunks) (*before_chunks)();
     // after_chunk: chunks end at block-column boundaries (crt_column_chunks)
     const std::vector<std::pair<uint64_t, uint64_t>> cols =
-        after_chunk ? crt_column_chunks(n, res_bytes) : std::vector<std::pair<uint64_t, uint64_t>>();
+        after_chunk ? crt_column_chunks(A.n, res_bytes) : std::vector<std::pair<uint64_t, uint64_t>>();
     size_t ci = 0;
     for (uint64_t b0 = 0, cnt = 0; b0 < total; b0 += cnt) {
         cnt = std::min(per, total - b0);
@@ -805,74 +845,30 @@ void launch_syrk_packed_crt(const uint8_t* packed, uint64_t pitch, uint64_t n, u
         SNPMI_REQUIRE(cnt < (1ull << 23), SNPMI_E_ARG, "crt SYRK: chunk too large");
         // the kR moduli of a block on one XCD at once (FETCH 951 -> 149 GB per 62.5k-SNP
         // launch at 50k iids, the clock 2.21 -> 2.36 GHz, -3.6%: profiles/r05m)
-        if (g_crt_kernel == 1)
-            k_syrk_i8w<SK><<<(unsigned)(round_up(cnt, 8) * kR), 768, 0, st>>>(packed, pitch, m, mpad, lutr, ctl, b0,
-                                                                            cnt, res, lgp, logs, part_tab);
-        else if (g_crt_kernel == 2)
-            k_syrk_i8w<SK, false, 0><<<(unsigned)(round_up(cnt, 8) * kR), 768, 0, st>>>(packed, pitch, m, mpad, lutr, ctl,
-                                                                                      b0, cnt, res, lgp, logs, part_tab);
-        else
-            k_syrk_i8r<SK><<<(unsigned)(round_up(cnt, 8) * kR), 512, 0, st>>>(packed, pitch, m, mpad, lutr, ctl, b0,
-                                                                            cnt, res, lgp, logs, part_tab);
-        k_crt<><<<(unsigned)(cnt * 64), 256, 0, st>>>(res, b0, cnt, n, ctl, F, cc, tiles, accumulate, part_tab, lgp, logs,
-                                                    rec);
+        const unsigned grid = (unsigned)(round_up(cnt, 8) * kR);
+        if (!B.P) {
+            if (g_crt_kernel == 1)
+                k_syrk_i8w<SK><<<grid, 768, 0, st>>>(A.P, A.pitch, m, w.mpad, w.lutr, w.ctl, b0, cnt, res, w.lga, logs,
+                                                   part_tab);
+            else if (g_crt_kernel == 2)
+                k_syrk_i8w<SK, false, 0><<<grid, 768, 0, st>>>(A.P, A.pitch, m, w.mpad, w.lutr, w.ctl, b0, cnt, res, w.lga,
+                                                             logs, part_tab);
+            else
+                k_syrk_i8r<SK><<<grid, 512, 0, st>>>(A.P, A.pitch, m, w.mpad, w.lutr, w.ctl, b0, cnt, res, w.lga, logs,
+                                                   part_tab);
+            k_crt<><<<(unsigned)(cnt * 64), 256, 0, st>>>(res, b0, cnt, A.n, w.ctl, F, cc, out, accumulate, part_tab, w.lga,
+                                                        logs, rec);
+        } else {
+            k_syrk_i8w<SK, true, 2, true><<<grid, 768, 0, st>>>(A.P, A.pitch, m, w.mpad, w.lutr, w.ctl, b0, cnt, res, w.lga,
+                                                              logs, nullptr, rb);
+            k_crt<true><<<(unsigned)(cnt * 64), 256, 0, st>>>(res, b0, cnt, A.n, w.ctl, F, cc, out, accumulate, nullptr, w.lga,
+                                                             logs, rec, rb);
+        }
         if (after_chunk) {
             SNPMI_HIP(hipGetLastError());
             (*after_chunk)(cols[ci].first, cols[ci].second);
             ci++;
         }
-    }
-    SNPMI_HIP(hipGetLastError());
-}
-
-// ctl | residue LUT | bound table | per-iid bound sums of A, then B | per-panel log2 bounds of A, then B
-uint64_t crt_rect_lut_bytes(uint64_t m, uint64_t n_a, uint64_t n_b) {
-    const uint64_t mpad = round_up(std::max<uint64_t>(m, 1), SK);
-    return 256 + (uint64_t)kR * mpad * 4 + mpad * 32 + (round_up(n_a, 2) + round_up(n_b, 2) + 2) * 8 +
-           (round_up(ceil_div(n_a, BW), 2) + round_up(ceil_div(n_b, BW), 2) + 2) * 8;
-}
-
-// The two-operand form of launch_syrk_packed_crt: blocks (+)= Za Zb^T as the dense 256 x 256 blocks
-// of the rectangle (slot bj * nba + bi).  The LUT tables are built once; the bound sums and panel
-// bounds once per operand (k_crt_bound, k_crt_panels).  The launch-wide R of hook "crt_block" = 0
-// comes from the larger of the two operands' maxima (sqrt(Ma Mb) <= max(Ma, Mb)).
-void launch_syrk_rect_crt(const uint8_t* Pa, uint64_t pitch_a, uint64_t n_a, const uint8_t* Pb, uint64_t pitch_b,
-                          uint64_t n_b, uint64_t m, const double* lut, double* blocks, int accumulate, void* ws_lut,
-                          uint8_t* res, uint64_t res_bytes, unsigned long long* rec, hipStream_t st) {
-    SNPMI_REQUIRE(m > 0 && m <= crt_max_snps(), SNPMI_E_ARG, "crt SYRK: SNP count per launch out of range");
-    const uint64_t total = rect_blocks(n_a, pitch_a, n_b, pitch_b);
-    if (total == 0) return;
-    const uint64_t nba = ceil_div(n_a, BW), nbb = ceil_div(n_b, BW), mpad = round_up(m, SK);
-    int* ctl = (int*)ws_lut;
-    uint32_t* lutr = (uint32_t*)((uint8_t*)ws_lut + 256);
-    double* qsq = (double*)(lutr + (uint64_t)kR * mpad);
-    double* Sa = qsq + 4 * mpad;
-    double* Sb = Sa + round_up(n_a, 2);
-    double* lga = Sb + round_up(n_b, 2);
-    double* lgb = lga + round_up(nba, 2);
-    const int F = crt_fraction_bits(m);
-    k_crt_exp<<<1, 1024, 0, st>>>(lut, 4 * m, ctl);
-    k_crt_lut<<<(unsigned)ceil_div(mpad, 256), 256, 0, st>>>(lut, m, mpad, F, ctl, lutr, qsq);
-    SNPMI_HIP(hipMemsetAsync(Sa, 0, (round_up(n_a, 2) + round_up(n_b, 2)) * sizeof(double), st));
-    k_crt_bound<<<dim3((unsigned)ceil_div(ceil_div(n_a, 16), 256), (unsigned)ceil_div(m, kBoundSlice)), 256, 0, st>>>(
-        Pa, pitch_a, n_a, m, qsq, ctl, Sa);
-    k_crt_bound<<<dim3((unsigned)ceil_div(ceil_div(n_b, 16), 256), (unsigned)ceil_div(m, kBoundSlice)), 256, 0, st>>>(
-        Pb, pitch_b, n_b, m, qsq, ctl, Sb);
-    static const CrtLog logs0 = crt_logs();
-    CrtLog logs = logs0;
-    logs.per_block = g_crt_block;
-    k_crt_r<<<1, 1024, 0, st>>>(Sa, round_up(n_a, 2) + n_b, logs, ctl, rec);
-    k_crt_panels<<<(unsigned)nba, 256, 0, st>>>(Sa, n_a, ctl, lga);
-    k_crt_panels<<<(unsigned)nbb, 256, 0, st>>>(Sb, n_b, ctl, lgb);
-    const uint64_t per = std::min<uint64_t>(std::max<uint64_t>(1, res_bytes / ((uint64_t)kR * BW * BW)), (1ull << 23) - 8);
-    static const CrtConst cc = crt_constants();
-    const RectArg<true> rb{Pb, pitch_b, (uint32_t)nba, lgb};
-    for (uint64_t b0 = 0, cnt = 0; b0 < total; b0 += cnt) {
-        cnt = std::min(per, total - b0);
-        k_syrk_i8w<SK, true, 2, true><<<(unsigned)(round_up(cnt, 8) * kR), 768, 0, st>>>(Pa, pitch_a, m, mpad, lutr, ctl, b0,
-                                                                                       cnt, res, lga, logs, nullptr, rb);
-        k_crt<true><<<(unsigned)(cnt * 64), 256, 0, st>>>(res, b0, cnt, n_a, ctl, F, cc, blocks, accumulate, nullptr, lga,
-                                                         logs, rec, rb);
     }
     SNPMI_HIP(hipGetLastError());
 }

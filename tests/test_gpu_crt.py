@@ -218,3 +218,144 @@ def _forms_bit_identical(hook, n, m, parts, forms=(0, 1)):
         finally:
             N.call("snpmi_set_kernel_variant", hook, 1)
     assert outs[0].size and all(np.array_equal(outs[0], o) for o in outs[1:])
+
+
+# ------------------------------------------------------------------ the f64 step loop (crt_max_snps() SNPs per step)
+STEP_N, STEP_M = 300, 65536 + 300  # the smallest shape that crosses one step boundary
+
+
+@pytest.fixture(scope="module")
+def step_data():
+    """Synthetic codes of STEP_M SNPs with their f64 Unit LUT, shared by the step-loop tests."""
+    from test_gpu_parity import Dev, synth_dev
+
+    buf, pitch = synth_dev(STEP_N, STEP_M, 41)
+    lut, st = Dev(STEP_M * 32), Dev(STEP_M * 16)
+    N.call("snpmi_dev_snp_stats", buf.p, pitch, STEP_N, STEP_M, 0, N.STD_UNIT, 0.0, 0.0, 0, N.DT_F64, st.p, lut.p)
+    return buf, pitch, lut
+
+
+def _step_dest(dest, n):
+    """(bytes of the destination, launch(ptr, pitch, m, lut, dst, accumulate), entries(raw) -> the
+    K entries only: pad rows / columns (iid >= n) are scratch)."""
+    nb = (n + 255) // 256
+    if dest == "whole":
+        nt = (n + 127) // 128
+        tj = np.repeat(np.arange(nt), np.arange(1, nt + 1))
+        ti = np.concatenate([np.arange(j + 1) for j in range(nt)])
+        vc = n - (nt - 1) * 128
+
+        def entries(x):
+            T = x.reshape(-1, 128, 128).copy()
+            T[tj == nt - 1, :, vc:] = 0
+            T[ti == nt - 1, vc:, :] = 0
+            return T
+
+        def launch(p, pitch, m, lut, dst, acc):
+            N.call("snpmi_dev_syrk_packed", p, pitch, n, m, lut, N.DT_F64, dst, acc)
+
+        return N.lib().snpmi_grm_tile_bytes(n, N.DT_F64), launch, entries
+    if dest == "rect":
+        def entries(x):  # slot bj * nba + bi
+            B = x.reshape(nb, nb, 256, 256).transpose(1, 2, 0, 3).reshape(nb * 256, nb * 256)
+            return B[:n, :n].copy()
+
+        def launch(p, pitch, m, lut, dst, acc):
+            N.call("snpmi_dev_syrk_rect", p, pitch, n, p, pitch, n, m, lut, N.DT_F64, dst, acc, None, 0)
+
+        return N.lib().snpmi_grm_rect_bytes(n, n, N.DT_F64), launch, entries
+    assert dest == "part"  # rank 0 of world 1: every upper-triangle block, dense
+    nloc = N.lib().snpmi_grm_part_blocks(n, 0, 1)
+    coords = np.empty((nloc, 2), dtype=np.uint64)
+    N.call("snpmi_grm_part_coords_all", n, 0, 1, N.ptr(coords))
+
+    def entries(x):
+        B = x.reshape(nloc, 256, 256).copy()
+        for w, (r0, c0) in enumerate(coords.astype(np.int64)):
+            B[w, max(0, n - r0):, :] = 0
+            B[w, :, max(0, n - c0):] = 0
+        return B
+
+    def launch(p, pitch, m, lut, dst, acc):
+        N.call("snpmi_dev_syrk_packed_part_f64", p, pitch, n, m, lut, 0, 1, dst, acc)
+
+    return nloc * 65536 * 8, launch, entries
+
+
+@pytest.mark.parametrize("dest,f64_mfma", [("whole", 0), ("rect", 0), ("part", 0), ("rect", 1), ("part", 1)])
+def test_f64_step_loop_is_two_accumulating_calls(step_data, dest, f64_mfma):
+    """One call over 65536 + 300 SNPs runs two steps; it performs exactly the launches of a call
+    over the first 65536 SNPs (accumulate = 0) and one over the rest (accumulate = 1), so K is the
+    same bits -- into the whole K, a rectangle (both operands every iid) and a part.  Hook "f64" =
+    1 repeats it off the CRT path for the rectangle and the part, which keep the step loop there
+    (the whole K is then a single launch of the f64 MFMA path, no steps)."""
+    from test_gpu_parity import Dev
+
+    buf, pitch, lut = step_data
+    n, m, lead = STEP_N, STEP_M, 65536
+    nbytes, launch, entries = _step_dest(dest, n)
+    one, two = Dev(nbytes), Dev(nbytes)
+    N.call("snpmi_set_kernel_variant", b"f64", f64_mfma)
+    try:
+        launch(buf.p, pitch, m, lut.p, one.p, 0)
+        launch(buf.p, pitch, lead, lut.p, two.p, 0)
+        launch(ctypes.c_void_p(buf.p.value + lead * pitch), pitch, m - lead, ctypes.c_void_p(lut.p.value + lead * 32),
+               two.p, 1)
+    finally:
+        N.call("snpmi_set_kernel_variant", b"f64", 0)
+    a = entries(one.get(np.empty(nbytes // 8, dtype=np.float64)))
+    b = entries(two.get(np.empty(nbytes // 8, dtype=np.float64)))
+    assert np.abs(a).max() > 0
+    assert np.array_equal(a, b)
+
+
+@pytest.fixture(scope="module")
+def step_bed(tmp_path_factory):
+    """A .bed of STEP_N x STEP_M with missing values, and its whole f64 K (Bed.read_kernel)."""
+    rng = np.random.default_rng(43)
+    v = rng.binomial(2, rng.uniform(0.05, 0.5, STEP_M), size=(STEP_N, STEP_M)).astype(np.float32)
+    v[rng.random(v.shape) < 0.01] = np.nan
+    path = str(tmp_path_factory.mktemp("step") / "s.bed")
+    Bed.write(path, SnpData(iid=[["f", str(i)] for i in range(STEP_N)], sid=["s%d" % j for j in range(STEP_M)], val=v),
+              count_A1=False)
+    return path, Bed(path, count_A1=False).read_kernel(Unit(), dtype=np.float64).val
+
+
+@pytest.mark.parametrize("f64_mfma", [0, 1])
+def test_f64_part_from_bed_matches_whole_kernel(step_bed, f64_mfma):
+    """snpmi_grm_part_bed_f64, rank 0 of world 1, over 65536 + 300 SNPs: the part's blocks placed by
+    snpmi_grm_part_coords_all equal Bed.read_kernel(Unit(), float64) of the same file within 1e-12
+    of the largest diagonal (test_gpu_partitioned_kernel.py's f64 bar) -- on the CRT path and, with
+    hook "f64" = 1, on the fused f64 MFMA kernel (the part's off-CRT branch of syrk_packed_auto).
+    The file stream hands over at most 65536 SNPs per chunk, so the step boundary itself is crossed
+    by the "part" cases of test_f64_step_loop_is_two_accumulating_calls."""
+    path, Kref = step_bed
+    n, m = STEP_N, STEP_M
+    nloc = N.lib().snpmi_grm_part_blocks(n, 0, 1)
+    coords = np.empty((nloc, 2), dtype=np.uint64)
+    N.call("snpmi_grm_part_coords_all", n, 0, 1, N.ptr(coords))
+    blocks, stats = np.empty((nloc, 256, 256), dtype=np.float64), np.empty((m, 2), dtype=np.float64)
+    N.call("snpmi_set_kernel_variant", b"f64", f64_mfma)
+    try:
+        N.call("snpmi_grm_part_bed_f64", path.encode(), n, m, 0, None, n, None, m, N.STD_UNIT, 0.0, 0.0, 0,
+               N.ptr(stats), 0, 1, N.ptr(blocks), 0)
+    finally:
+        N.call("snpmi_set_kernel_variant", b"f64", 0)
+    nb = (n + 255) // 256
+    K = np.zeros((nb * 256, nb * 256))
+    for blk, (i, j) in zip(blocks, coords.astype(np.int64)):
+        K[j:j + 256, i:i + 256] = blk.T
+        K[i:i + 256, j:j + 256] = blk
+    err = np.abs(K[:n, :n] - Kref).max() / np.abs(np.diag(Kref)).max()
+    print("part from bed, f64 hook", f64_mfma, "err", err)
+    assert err <= 1e-12, err
+
+
+def test_f64_part_pitch_error_is_unchanged():
+    """A part call whose pitch does not cover round_up(n, 256) iids is SNPMI_E_ARG with the text the
+    entry point has always given."""
+    from test_gpu_parity import Dev
+
+    d = Dev(1 << 20)
+    with pytest.raises(ValueError, match="^pitch must be snpmi_packed_pitch$"):
+        N.call("snpmi_dev_syrk_packed_part_f64", d.p, 64, 300, 8, d.p, 0, 1, d.p, 0)
