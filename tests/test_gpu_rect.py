@@ -69,7 +69,9 @@ def _operand(packed, pitch, idx, cnt):
     return dst, dst.p, po
 
 
-def _stateless(packed, pitch, rows, cols, dtype, cnt=m, exact_diag=True):
+def _stateless(packed, pitch, rows, cols, dtype, cnt=m, exact_diag=True, poison=False):
+    """poison: the blocks hold 0xFF bytes (NaN) before the launch, so an element it leaves unwritten
+    fails every comparison."""
     from pysnptools_amd.kernelreader.rect import diag_pairs
 
     dtype = np.dtype(dtype)
@@ -84,6 +86,8 @@ def _stateless(packed, pitch, rows, cols, dtype, cnt=m, exact_diag=True):
     pairs = diag_pairs(rows, cols, nr, nc) if exact_diag else np.empty((0, 2), np.uint32)
     K = np.empty((nr, nc), dtype=dtype)
     try:
+        if poison:
+            N.call("snpmi_dev_memset", blocks.p, 0xFF, nbytes)
         N.call("snpmi_dev_syrk_rect", pa, pitch_a, nr, pb, pitch_b, nc, cnt, lut.p, N.dt_code(dtype), blocks.p, 0,
                N.ptr(pairs) if len(pairs) else None, len(pairs))
         N.call("snpmi_dev_rect_extract", blocks.p, nr, nc, N.dt_code(dtype), 1, 1.0, N.ptr(K))
