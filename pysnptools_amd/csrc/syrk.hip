@@ -14,7 +14,7 @@
 //     per 128-iid tile) and expands them through the per-SNP 4-entry LUT written by
 //     k_snp_stats -- decode + Unit/Beta standardization fused into the GEMM staging, so the
 //     standardized Z never exists in HBM.  DENSE loader: an F-order float matrix (SnpData).
-#include "snpmi_internal.hpp"
+#include "syrk_device.hpp"
 
 #include <algorithm>
 #include <vector>
@@ -26,14 +26,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BM = kTile;  // 128
-
-__device__ __forceinline__ void tile_coords(uint64_t L, uint32_t& ti, uint32_t& tj) {
-    uint64_t j = (uint64_t)((sqrt(8.0 * (double)L + 1.0) - 1.0) * 0.5);
-    while ((j + 1) * (j + 2) / 2 <= L) j++;
-    while (j * (j + 1) / 2 > L) j--;
-    tj = (uint32_t)j;
-    ti = (uint32_t)(L - j * (j + 1) / 2);
-}
 
 // 4-entry LUT select, written so hipcc emits three v_cndmask (no divergent branches:
 // the nested-ternary form compiled to exec-mask branches around every element).
@@ -367,22 +359,14 @@ __global__ __launch_bounds__(512, 1) void k_syrk256(const uint8_t* __restrict__ 
 template <bool LOCAL = false>
 __global__ __launch_bounds__(512, 1) void k_syrk256d(const float* __restrict__ Z, uint64_t ldz, uint64_t n,
                                                     uint64_t kdim, float* __restrict__ tiles, int accumulate,
-                                                    uint32_t part_rank = 0, uint32_t part_world = 1,
                                                     const uint32_t* __restrict__ gate = nullptr,
                                                     const uint32_t* __restrict__ part_tab = nullptr) {
     constexpr int G = 2 * BK / 8;  // glds per wave per stage (8 waves, one 1 KiB row each)
     __shared__ __attribute__((aligned(16))) float lds[2][2][BK * LDA];
     if (gate && *gate == 0) return;  // fallback of the dense fp16x2 kernel (range flag raised)
     const uint64_t wg = blockIdx.x;
-    uint32_t bi, bj;
-    if constexpr (LOCAL) {  // slot wg of the part's layout table (part_layout)
-        bi = part_tab[wg] & 0xffffu;
-        bj = part_tab[wg] >> 16;
-    } else {
-        tile_coords(wg, bi, bj);
-    }
-    (void)part_rank;
-    (void)part_world;
+    uint32_t bi, bj;  // LOCAL: slot wg of the part's layout table (part_layout)
+    block_coords<false>(0, blockIdx.x, LOCAL, part_tab, RectArg<false>(), bi, bj);
     const uint64_t i0 = (uint64_t)bi * BW, j0 = (uint64_t)bj * BW;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave >> 2, wn = wave & 3;
@@ -471,6 +455,7 @@ constexpr int B3_PLANE = BK * B3_RS;           // bf16 per plane of one panel (B
 constexpr int B3_STAGE = 2 * 3 * B3_PLANE;     // bf16 per stage (2 panels x 3 planes)
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 typedef short i16x4_t __attribute__((ext_vector_type(4)));
 typedef short i16x8_t __attribute__((ext_vector_type(8)));
 
@@ -478,7 +463,68 @@ __device__ __forceinline__ i16x4_t lds_tr16(const short* p) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4_t*)p);
 }
 
-__device__ __forceinline__ int pi16(int p) { return 4 * (p & 3) + (p >> 2); }
+// ---- pieces the three packed kernels (k_syrk_bf3, k_syrk_h2, k_syrk_h2s) share; their stage /
+// prologue / loader-wave bodies, which order these against the MFMAs and barriers, stay per kernel.
+
+// How a launch maps onto K.  Grid y > 1 is split-K: slice y covers SNPs [y * kslice, + kslice)
+// into its own partial K at tiles + y * slice_elems.  Workgroup x is block wg0 + x of the full
+// grid's order (wg0 > 0: a column group, launch_syrk_packed_h2_cols): block identity, storage slot
+// and SegFlush phase follow that sum.  table: bi | bj << 16 per block -- a cfg5 part's layout
+// (LOCAL), else the supertile order of the fp16x2 kernels -- or nullptr: the triangle's own order.
+struct SyrkGrid {
+    uint64_t kslice = 0, slice_elems = 0;
+    uint64_t wg0 = 0;
+    const uint32_t* table = nullptr;
+};
+
+// split-K: move the operand, its split LUT (lut_words u32 per SNP), the SNP count and the
+// destination to slice blockIdx.y.  A template: the kernels' pointers are __restrict__.  The two
+// fp16 kernels call it; k_syrk_bf3 spells the same six lines out, because with the call its
+// register allocation changes (215 instead of 217 VGPRs, two scalar spills fewer).
+template <class PT, class LT, class TT>
+__device__ __forceinline__ void split_k_slice(const SyrkGrid& g, int lut_words, PT& P, uint64_t pitch, LT& lut,
+                                              uint64_t& kdim, TT& tiles) {
+    if (gridDim.y > 1) {
+        const uint64_t k0 = (uint64_t)blockIdx.y * g.kslice;
+        P += k0 * pitch;
+        lut += lut_words * k0;
+        kdim = min(g.kslice, kdim - k0);
+        tiles += (uint64_t)blockIdx.y * g.slice_elems;
+    }
+}
+
+// code word w (16 iids) -> the 8 v_perm selectors of its iid pairs ("Cheap expansion" above)
+__device__ __forceinline__ void code_selectors(uint32_t w, uint32_t (&sel)[8]) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const uint32_t v = (w >> (2 * j)) & 0x03030303u;  // byte q: code of iid 4q + j
+        const uint32_t o = v | 0x04040404u;
+        sel[2 * j] = __builtin_amdgcn_perm(o, v, 0x05010400u);      // iids (j, 4 + j)
+        sel[2 * j + 1] = __builtin_amdgcn_perm(o, v, 0x07030602u);  // iids (8 + j, 12 + j)
+    }
+}
+
+// MFMA operand fragment (V = bf16x8_t / f16x8_t): 8 k-rows x the lane's iid, two transposed reads
+template <class V>
+__device__ __forceinline__ V frag16(const short* b) {
+    const i16x4_t r0 = lds_tr16(b), r1 = lds_tr16(b + 4 * B3_RS);
+    return __builtin_bit_cast(V, (i16x8_t)__builtin_shufflevector(r0, r1, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
+// one product of two planes over 16 SNPs: the wave's 4 x 2 MFMAs.  The kernels call it through a
+// local lambda: called directly, k_syrk_h2s needs 168 instead of 165 VGPRs.
+__device__ __forceinline__ void mfma_group(f32x16 (&acc)[4][2], const bf16x8_t (&a)[4], const bf16x8_t (&b)[2]) {
+#pragma unroll
+    for (int x = 0; x < 4; x++)
+#pragma unroll
+        for (int y = 0; y < 2; y++) acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[x], b[y], acc[x][y], 0, 0, 0);
+}
+__device__ __forceinline__ void mfma_group(f32x16 (&acc)[4][2], const f16x8_t (&a)[4], const f16x8_t (&b)[2]) {
+#pragma unroll
+    for (int x = 0; x < 4; x++)
+#pragma unroll
+        for (int y = 0; y < 2; y++) acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[x], b[y], acc[x][y], 0, 0, 0);
+}
 
 // f32w::epilogue with the pi-permuted rows/columns of k_syrk_bf3
 template <bool LOCAL>
@@ -593,9 +639,9 @@ struct SegFlush {
                     }
         }
 #pragma unroll
-        for (int x = 0; x < 4; x++)
+    for (int x = 0; x < 4; x++)
 #pragma unroll
-            for (int y = 0; y < 2; y++) a[x][y] = (f32x16){};
+        for (int y = 0; y < 2; y++) a[x][y] = (f32x16){};
         any = true;
     }
     // before the final epilogue: add the flushed segments back into the accumulators
@@ -633,33 +679,22 @@ struct B3Regs {
 template <bool LOCAL = false, bool RECT = false>
 __global__ __launch_bounds__(512, 1) void k_syrk_bf3(const uint8_t* __restrict__ P, uint64_t pitch, uint64_t n,
                                                      uint64_t kdim, const uint32_t* __restrict__ lut3,
-                                                     float* __restrict__ tiles, int accumulate,
-                                                     uint32_t part_rank = 0, uint32_t part_world = 1,
-                                                     uint64_t kslice = 0, uint64_t slice_elems = 0,
-                                                     const uint32_t* __restrict__ gate = nullptr, SegCtx seg = SegCtx(),
-                                                     uint64_t wg0 = 0, const uint32_t* __restrict__ part_tab = nullptr,
+                                                     const uint32_t* __restrict__ gate, float* __restrict__ tiles,
+                                                     int accumulate, SyrkGrid grid, SegCtx seg,
                                                      RectArg<RECT> rb = RectArg<RECT>()) {
     __shared__ __attribute__((aligned(16))) short lds[2 * B3_STAGE];
     if (gate && *gate == 0) return;  // fallback of k_syrk_h2: runs only when its range flag is set
-    if (gridDim.y > 1) {  // split-K: slice blockIdx.y covers SNPs [y*kslice, +kslice) into its own partial K
-        const uint64_t k0 = (uint64_t)blockIdx.y * kslice;
+    if (gridDim.y > 1) {  // split_k_slice(grid, 8, ...), spelled out: see there
+        const uint64_t k0 = (uint64_t)blockIdx.y * grid.kslice;
         P += k0 * pitch;
         lut3 += 8 * k0;
-        kdim = min(kslice, kdim - k0);
-        tiles += (uint64_t)blockIdx.y * slice_elems;
+        kdim = min(grid.kslice, kdim - k0);
+        tiles += (uint64_t)blockIdx.y * grid.slice_elems;
     }
-    // wg0: first block of a column-group launch (triangular order), as in k_syrk_h2
-    const uint64_t wg = wg0 + blockIdx.x;
+    // the table only as a part's layout (LOCAL); otherwise this kernel walks the triangle itself
+    const uint64_t wg = grid.wg0 + blockIdx.x;
     uint32_t bi, bj;
-    if constexpr (RECT) {  // two operands: every block of the rectangle, bi fastest inside bj
-        bi = (uint32_t)(wg % rb.nba);
-        bj = (uint32_t)(wg / rb.nba);
-    } else if constexpr (LOCAL) {  // slot wg of the part's layout table (part_layout)
-        bi = part_tab[wg] & 0xffffu;
-        bj = part_tab[wg] >> 16;
-    } else {
-        tile_coords(wg, bi, bj);
-    }
+    block_coords<RECT>(wg, 0, LOCAL, grid.table, rb, bi, bj);
     const uint64_t i0 = (uint64_t)bi * BW, j0 = (uint64_t)bj * BW;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wm = wave >> 2, wn = wave & 3;
@@ -703,15 +738,6 @@ __global__ __launch_bounds__(512, 1) void k_syrk_bf3(const uint8_t* __restrict__
         r.la = *reinterpret_cast<const uint4*>(lp3 + 8 * BK * st);
         r.lb = *reinterpret_cast<const uint4*>(lp3 + 8 * BK * st + 4);
     };
-    auto make_sel = [&](uint32_t w, uint32_t (&sel)[8]) {
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const uint32_t v = (w >> (2 * j)) & 0x03030303u;  // byte q: code of iid 4q + j
-            const uint32_t o = v | 0x04040404u;
-            sel[2 * j] = __builtin_amdgcn_perm(o, v, 0x05010400u);      // iids (j, 4 + j)
-            sel[2 * j + 1] = __builtin_amdgcn_perm(o, v, 0x07030602u);  // iids (8 + j, 12 + j)
-        }
-    };
     auto store_plane = [&](short* S, int pl, const B3Regs& r, const uint32_t (&sel)[8]) {
         const uint32_t lo = pl == 0 ? r.la.x : pl == 1 ? r.la.z : r.lb.x;
         const uint32_t hi = pl == 0 ? r.la.y : pl == 1 ? r.la.w : r.lb.y;
@@ -730,14 +756,12 @@ __global__ __launch_bounds__(512, 1) void k_syrk_bf3(const uint8_t* __restrict__
     };
     auto store = [&](short* S, const B3Regs& r) {
         uint32_t sel[8];
-        make_sel(r.w, sel);
+        code_selectors(r.w, sel);
 #pragma unroll
         for (int pl = 0; pl < 3; pl++) store_plane(S, pl, r, sel);
     };
     auto frag = [&](const short* S, int panel, int pl, int col, int off) -> bf16x8_t {
-        const short* b = S + (panel * 3 + pl) * B3_PLANE + off + col;
-        const i16x4_t r0 = lds_tr16(b), r1 = lds_tr16(b + 4 * B3_RS);
-        return __builtin_bit_cast(bf16x8_t, (i16x8_t)__builtin_shufflevector(r0, r1, 0, 1, 2, 3, 4, 5, 6, 7));
+        return frag16<bf16x8_t>(S + (panel * 3 + pl) * B3_PLANE + off + col);
     };
     {
         // The loader with the workgroup barrier in the middle of the stage: after
@@ -755,13 +779,7 @@ __global__ __launch_bounds__(512, 1) void k_syrk_bf3(const uint8_t* __restrict__
 #pragma unroll
             for (int x = 0; x < 4; x++) a[x] = frag(S, 0, pa, wm * 128 + 32 * x, x >= 2 ? rd_off + dswz : rd_off);
         };
-        auto group = [&](const bf16x8_t (&a)[4], const bf16x8_t (&b)[2]) {
-#pragma unroll
-            for (int x = 0; x < 4; x++)
-#pragma unroll
-                for (int y = 0; y < 2; y++)
-                    acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[x], b[y], acc[x][y], 0, 0, 0);
-        };
+        auto group = [&](const bf16x8_t (&a)[4], const bf16x8_t (&b)[2]) { mfma_group(acc, a, b); };
         B3Regs r;
         load(0, r);
         store(lds, r);
@@ -779,7 +797,6 @@ __global__ __launch_bounds__(512, 1) void k_syrk_bf3(const uint8_t* __restrict__
         // 303.3-307.1 TFLOP/s with the barrier-guarded form; 2 or 3 VALU per MFMA 305-307,
         // unconditional hooks without the pin 306.1, + the next B reads pinned between the
         // group 4-5 MFMAs 293.4 (profiles/r01i/ubench_syrk_bf3_interleave.jsonl).
-        constexpr bool kUncond = true;
         auto pin = [&]() {
 #pragma unroll
             for (int i = 0; i < 8; i++) {
@@ -790,32 +807,28 @@ __global__ __launch_bounds__(512, 1) void k_syrk_bf3(const uint8_t* __restrict__
         auto stage = [&](uint64_t s, bf16x8_t (&B0)[2], bf16x8_t (&B1)[2], bf16x8_t (&B0n)[2], bf16x8_t (&B1n)[2]) {
             const short* cur = lds + (s & 1) * B3_STAGE;
             short* nxt = lds + ((s + 1) & 1) * B3_STAGE;
-            const bool more = kUncond || s + 1 < nst;
             bf16x8_t A0[4], B2[2], A1[4], A2[4];
             fragsA(cur, 0, A0);
             fragB(cur, 2, B2);
             fragsA(cur, 1, A1);
             uint32_t sel[8];
             group(A0, B0);
-            if (more) make_sel(r.w, sel);
+            code_selectors(r.w, sel);
             pin();
             group(A0, B1);
-            if (more) store_plane(nxt, 0, r, sel);
+            store_plane(nxt, 0, r, sel);
             pin();
             group(A0, B2);
             fragsA(cur, 2, A2);
-            if (more) store_plane(nxt, 1, r, sel);
+            store_plane(nxt, 1, r, sel);
             pin();
             group(A1, B0);
-            if (more) store_plane(nxt, 2, r, sel);
+            store_plane(nxt, 2, r, sel);
             pin();
-            if constexpr (kUncond) load(s + 2 < nst ? s + 2 : nst - 1, r);
-            else if (more && s + 2 < nst) load(s + 2, r);
+            load(s + 2 < nst ? s + 2 : nst - 1, r);
             __syncthreads();
-            if (more) {
-                fragB(nxt, 0, B0n);
-                fragB(nxt, 1, B1n);
-            }
+            fragB(nxt, 0, B0n);
+            fragB(nxt, 1, B1n);
             group(A1, B1);
             group(A2, B0);
         };
@@ -969,8 +982,6 @@ __global__ __launch_bounds__(256) void k_image_h2(const float* __restrict__ Z, u
     }
 }
 
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-
 // Same block structure, loader roles and LDS image as k_syrk_bf3 (two fp16 planes per panel
 // instead of three bf16 planes); per 16-SNP k-step each wave runs 3 groups of 8
 // v_mfma_f32_32x32x16_f16: (A0,B0), (A0,B1), (A1,B0).  Runs only when *flag == 0 (see k_lut_h2).
@@ -982,50 +993,29 @@ typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 // group then hit 32 distinct banks (the 16-B-half swap the ds_write_b128 form needed left them 2-way
 // conflicted, PMC SQ_LDS_BANK_CONFLICT = 29% of SQ_LDS_IDX_ACTIVE, profiles/r04n); the transposed
 // fragment reads undo the rotation per lane.  k_syrk_h2s (below) is the same kernel with the loader
-// in its own waves -- the default since round 6; this form stays for the split-K grids and as
-// hook "h2" = 0.
+// in its own waves -- the default since round 6, for whole-K, column-group, part and split-K grids
+// alike; this form stays as hook "h2" = 0.
 // MODE 6 (DENSE): the operand is a dense float block already rewritten by k_image_h2 as stage
 // images (the exact LDS rows the packed loader would build, swap layout), moved into LDS by
-// LDS-DMA.
+// LDS-DMA; it has no LUT, and lut2 is its block order table instead (supertile_order: the 256
+// blocks in flight share 32 panels).  Read from grid.table, the kernel's instructions change.
 template <bool LOCAL = false, int MODE = 4, bool DENSE = false>
 __global__ __launch_bounds__(512, 1) void k_syrk_h2(const uint8_t* __restrict__ P, uint64_t pitch, uint64_t n,
                                                     uint64_t kdim, const uint32_t* __restrict__ lut2,
                                                     const uint32_t* __restrict__ flag, float* __restrict__ tiles,
-                                                    int accumulate, uint32_t part_rank = 0, uint32_t part_world = 1,
-                                                    uint64_t kslice = 0, uint64_t slice_elems = 0,
-                                                    SegCtx seg = SegCtx(), const uint32_t* __restrict__ order = nullptr,
-                                                    uint64_t wg0 = 0) {
+                                                    int accumulate, SyrkGrid grid, SegCtx seg) {
     static_assert(MODE == 4 || (MODE == 6 && DENSE), "k_syrk_h2: MODE 4 (packed) or MODE 6 (dense stage images)");
-    // wg0: first block of this launch in the full grid's order (a column group of the triangle,
-    // launch_syrk_packed_h2_cols); block identity, storage and SegFlush phase follow wg0 + blockIdx.x
     constexpr int KS = 2, SBK = KS * BK;  // two 16-SNP k-steps per LDS stage
     constexpr int PLANE = KS * B3_PLANE, STAGE = 2 * 2 * PLANE;
     constexpr bool kRot = MODE == 4;
     __shared__ __attribute__((aligned(16))) short lds[2 * STAGE];
     if (*flag) return;  // a SNP of this block is outside fp16's range: k_syrk_bf3 runs instead
-    if (gridDim.y > 1) {
-        const uint64_t k0 = (uint64_t)blockIdx.y * kslice;
-        P += k0 * pitch;
-        lut2 += 4 * k0;
-        kdim = min(kslice, kdim - k0);
-        tiles += (uint64_t)blockIdx.y * slice_elems;
-    }
-    const uint64_t wg = wg0 + blockIdx.x;
+    split_k_slice(grid, 4, P, pitch, lut2, kdim, tiles);
+    // table: block order (supertile_order) / the part's layout (part_layout), whose slot wg is
+    // also the block's storage slot
+    const uint64_t wg = grid.wg0 + blockIdx.x;
     uint32_t bi, bj;
-    if constexpr (DENSE) {
-        // lut2 = block order table (supertile_order): the 256 blocks in flight share 32 panels
-        const uint32_t c = lut2[wg];
-        bi = c & 0xffffu;
-        bj = c >> 16;
-    } else if (LOCAL || order) {  // block order table (supertile_order) / the part's layout table (part_layout)
-        const uint32_t c = order[wg];
-        bi = c & 0xffffu;
-        bj = c >> 16;
-    } else {
-        tile_coords(wg, bi, bj);
-    }
-    // LOCAL: slot wg of the part's layout table is the block's storage slot and SegFlush phase
-    const uint64_t blk = wg;
+    block_coords<false>(wg, 0, DENSE || LOCAL || grid.table, DENSE ? lut2 : grid.table, RectArg<false>(), bi, bj);
     const uint64_t i0 = (uint64_t)bi * BW, j0 = (uint64_t)bj * BW;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wm = wave >> 2, wn = wave & 3;
@@ -1061,21 +1051,13 @@ __global__ __launch_bounds__(512, 1) void k_syrk_h2(const uint8_t* __restrict__ 
             rl[h] = *reinterpret_cast<const uint4*>(lp2 + 4 * (SBK * st + h * BK));
         }
     };
-    auto make_sel = [&](uint32_t w, uint32_t (&sel)[8]) {
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const uint32_t v = (w >> (2 * j)) & 0x03030303u;
-            const uint32_t o = v | 0x04040404u;
-            sel[2 * j] = __builtin_amdgcn_perm(o, v, 0x05010400u);
-            sel[2 * j + 1] = __builtin_amdgcn_perm(o, v, 0x07030602u);
-        }
-    };
     auto store_plane = [&](short* S, int pl, int h, const uint32_t (&sel)[8]) {
         const uint32_t lo = pl == 0 ? rl[h].x : rl[h].z;
         const uint32_t hi = pl == 0 ? rl[h].y : rl[h].w;
         // two ds_write_b64 per 16-B half (6 LDS-transfer cycles per wave-instruction vs 13 for
         // ds_write_b128; volatile + explicit LDS address space so they are neither re-merged nor
-        // turned into flat stores): +1.2-1.3%, bit-identical K (profiles/r03crt/ubench_lds_store_width.jsonl)
+        // turned into flat stores): +1.2-1.3%, bit-identical K (profiles/r03crt/ubench_lds_store_width.jsonl).
+        // k_syrk_h2s has the same store; as a shared function it reorders that kernel's loader waves.
         typedef __attribute__((address_space(3))) volatile uint64_t lds_u64;
         lds_u64* qq = (lds_u64*)(S + (lp * 2 + pl) * PLANE + (lk + BK * h) * B3_RS + 16 * ld_);
 #pragma unroll
@@ -1084,9 +1066,7 @@ __global__ __launch_bounds__(512, 1) void k_syrk_h2(const uint8_t* __restrict__ 
                                  ((uint64_t)__builtin_amdgcn_perm(hi, lo, sel[2 * j + 1]) << 32);
     };
     auto frag = [&](const short* S, int panel, int pl, int h, int col, int off) -> f16x8_t {
-        const short* b = S + (panel * 2 + pl) * PLANE + h * BK * B3_RS + off + col;
-        const i16x4_t r0 = lds_tr16(b), r1 = lds_tr16(b + 4 * B3_RS);
-        return __builtin_bit_cast(f16x8_t, (i16x8_t)__builtin_shufflevector(r0, r1, 0, 1, 2, 3, 4, 5, 6, 7));
+        return frag16<f16x8_t>(S + (panel * 2 + pl) * PLANE + h * BK * B3_RS + off + col);
     };
     auto fragB = [&](const short* S, int pl, int h, f16x8_t (&b)[2]) {
 #pragma unroll
@@ -1096,13 +1076,7 @@ __global__ __launch_bounds__(512, 1) void k_syrk_h2(const uint8_t* __restrict__ 
 #pragma unroll
         for (int x = 0; x < 4; x++) a[x] = frag(S, 0, pa, h, wm * 128 + 32 * x, x >= 2 ? rd_offA1 : rd_offA0);
     };
-    auto group = [&](const f16x8_t (&a)[4], const f16x8_t (&b)[2]) {
-#pragma unroll
-        for (int x = 0; x < 4; x++)
-#pragma unroll
-            for (int y = 0; y < 2; y++)
-                acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[x], b[y], acc[x][y], 0, 0, 0);
-    };
+    auto group = [&](const f16x8_t (&a)[4], const f16x8_t (&b)[2]) { mfma_group(acc, a, b); };
     __shared__ uint32_t seg_slot;
     if constexpr (MODE == 6) {
         // DENSE stage images (k_image_h2): P = [16-SNP step t][256-iid block b][plane][16 rows x
@@ -1126,7 +1100,7 @@ __global__ __launch_bounds__(512, 1) void k_syrk_h2(const uint8_t* __restrict__ 
         issue(0, lds);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        SegFlush sf(seg, SBK, blk, nst, &seg_slot);
+        SegFlush sf(seg, SBK, wg, nst, &seg_slot);
         for (uint64_t s = 0; s < nst; s++) {
             const short* cur = lds + (s & 1) * STAGE;
             if (s + 1 < nst) issue(s + 1, lds + ((s + 1) & 1) * STAGE);
@@ -1146,23 +1120,22 @@ __global__ __launch_bounds__(512, 1) void k_syrk_h2(const uint8_t* __restrict__ 
             if (sf.due(s + 1 < nst)) sf.flush(acc);
         }
         sf.finish(acc);
-        epilogue_pi<LOCAL>(acc, tiles, n, bi, bj, accumulate, lane, wm, wn, blk);
+        epilogue_pi<LOCAL>(acc, tiles, n, bi, bj, accumulate, lane, wm, wn, wg);
         sf.release(seg);
         return;
     }
     // f32 accuracy: SegFlush (above) cuts the accumulation chains every seg SNPs inside this loop.
-    const uint64_t send = nst;  // the loader clamps its stage index to send - 1
     f16x8_t B0s[2], B1s[2], B0t[2], B1t[2];
     auto prologue = [&](uint64_t s0) {
         load(s0);
 #pragma unroll
         for (int h = 0; h < KS; h++) {
             uint32_t sel[8];
-            make_sel(rw[h], sel);
+            code_selectors(rw[h], sel);
             store_plane(lds, 0, h, sel);
             store_plane(lds, 1, h, sel);
         }
-        load(s0 + 1 < send ? s0 + 1 : send - 1);
+        load(s0 + 1 < nst ? s0 + 1 : nst - 1);
         __syncthreads();
         fragB(lds, 0, 0, B0s);
         fragB(lds, 1, 0, B1s);
@@ -1180,7 +1153,7 @@ __global__ __launch_bounds__(512, 1) void k_syrk_h2(const uint8_t* __restrict__ 
         fragsA(cur, 1, 0, Ay);
         uint32_t sel[8];
         group(Ax, B0);
-        make_sel(rw[0], sel);
+        code_selectors(rw[0], sel);
         store_plane(nxt, 0, 0, sel);
         group(Ax, B1);
         store_plane(nxt, 1, 0, sel);
@@ -1188,19 +1161,19 @@ __global__ __launch_bounds__(512, 1) void k_syrk_h2(const uint8_t* __restrict__ 
         fragB(cur, 1, 1, C1);
         fragsA(cur, 0, 1, Ax);
         group(Ay, B0);
-        make_sel(rw[1], sel);
+        code_selectors(rw[1], sel);
         store_plane(nxt, 0, 1, sel);
         fragsA(cur, 1, 1, Ay);
         group(Ax, C0);
         store_plane(nxt, 1, 1, sel);
         group(Ax, C1);
-        load(s + 2 < send ? s + 2 : send - 1);
+        load(s + 2 < nst ? s + 2 : nst - 1);
         __syncthreads();
         fragB(nxt, 0, 0, B0n);
         fragB(nxt, 1, 0, B1n);
         group(Ay, C0);
     };
-    SegFlush sf(seg, 2 * SBK, blk, (nst + 1) / 2, &seg_slot);
+    SegFlush sf(seg, 2 * SBK, wg, (nst + 1) / 2, &seg_slot);
     prologue(0);
     for (uint64_t s = 0; s < nst; s += 2) {
         stage(s, B0s, B1s, B0t, B1t);
@@ -1208,7 +1181,7 @@ __global__ __launch_bounds__(512, 1) void k_syrk_h2(const uint8_t* __restrict__ 
         if (sf.due(s + 2 < nst)) sf.flush(acc);
     }
     sf.finish(acc);
-    epilogue_pi<LOCAL>(acc, tiles, n, bi, bj, accumulate, lane, wm, wn, blk);
+    epilogue_pi<LOCAL>(acc, tiles, n, bi, bj, accumulate, lane, wm, wn, wg);
     sf.release(seg);
 }
 
@@ -1223,39 +1196,21 @@ template <bool LOCAL = false, bool RECT = false>
 __global__ __launch_bounds__(768, 1) void k_syrk_h2s(const uint8_t* __restrict__ P, uint64_t pitch, uint64_t n,
                                                      uint64_t kdim, const uint32_t* __restrict__ lut2,
                                                      const uint32_t* __restrict__ flag, float* __restrict__ tiles,
-                                                     int accumulate, uint32_t part_rank = 0, uint32_t part_world = 1,
-                                                     uint64_t kslice = 0, uint64_t slice_elems = 0,
-                                                     SegCtx seg = SegCtx(), const uint32_t* __restrict__ order = nullptr,
-                                                     uint64_t wg0 = 0, RectArg<RECT> rb = RectArg<RECT>()) {
+                                                     int accumulate, SyrkGrid grid, SegCtx seg,
+                                                     RectArg<RECT> rb = RectArg<RECT>()) {
     constexpr int KS = 2, SBK = KS * BK;
     constexpr int PLANE = KS * B3_PLANE, STAGE = 2 * 2 * PLANE;
     __shared__ __attribute__((aligned(16))) short lds[2 * STAGE];
     if (*flag) return;  // a SNP of this block is outside fp16's range: k_syrk_bf3 runs instead
-    if (gridDim.y > 1) {
-        const uint64_t k0 = (uint64_t)blockIdx.y * kslice;
-        P += k0 * pitch;
-        lut2 += 4 * k0;
-        kdim = min(kslice, kdim - k0);
-        tiles += (uint64_t)blockIdx.y * slice_elems;
-    }
-    const uint64_t wg = wg0 + blockIdx.x;
+    split_k_slice(grid, 4, P, pitch, lut2, kdim, tiles);
+    const uint64_t wg = grid.wg0 + blockIdx.x;
     uint32_t bi, bj;
-    if constexpr (RECT) {  // two operands: every block of the rectangle, bi fastest inside bj
-        bi = (uint32_t)(wg % rb.nba);
-        bj = (uint32_t)(wg / rb.nba);
-    } else if (LOCAL || order) {
-        const uint32_t c = order[wg];
-        bi = c & 0xffffu;
-        bj = c >> 16;
-    } else {
-        tile_coords(wg, bi, bj);
-    }
-    const uint64_t blk = wg;
+    block_coords<RECT>(wg, 0, LOCAL || grid.table, grid.table, rb, bi, bj);
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const uint64_t nst = (kdim + SBK - 1) / SBK;
     __shared__ uint32_t seg_slot;
-    SegFlush sf(seg, 2 * SBK, blk, (nst + 1) / 2, &seg_slot);  // every wave: it holds a barrier
+    SegFlush sf(seg, 2 * SBK, wg, (nst + 1) / 2, &seg_slot);  // every wave: it holds a barrier
     if (wave >= 8) {
         // loader thread lt = (panel lp, SNP rows lk + 8u of the stage (u < 4), 16-iid group ld_)
         const int lt = t - 512;
@@ -1284,15 +1239,9 @@ __global__ __launch_bounds__(768, 1) void k_syrk_h2s(const uint8_t* __restrict__
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 uint32_t sel[8];
+                code_selectors(rw[u], sel);
 #pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const uint32_t v = (rw[u] >> (2 * j)) & 0x03030303u;
-                    const uint32_t o = v | 0x04040404u;
-                    sel[2 * j] = __builtin_amdgcn_perm(o, v, 0x05010400u);
-                    sel[2 * j + 1] = __builtin_amdgcn_perm(o, v, 0x07030602u);
-                }
-#pragma unroll
-                for (int pl = 0; pl < 2; pl++) {
+                for (int pl = 0; pl < 2; pl++) {  // k_syrk_h2's store_plane, for 4 rows
                     const uint32_t lo = pl == 0 ? rl[u].x : rl[u].z;
                     const uint32_t hi = pl == 0 ? rl[u].y : rl[u].w;
                     typedef __attribute__((address_space(3))) volatile uint64_t lds_u64;
@@ -1327,17 +1276,9 @@ __global__ __launch_bounds__(768, 1) void k_syrk_h2s(const uint8_t* __restrict__
 #pragma unroll
         for (int y = 0; y < 2; y++) acc[x][y] = (f32x16){};
     auto frag = [&](const short* S, int panel, int pl, int h, int col, int off) -> f16x8_t {
-        const short* b = S + (panel * 2 + pl) * PLANE + h * BK * B3_RS + off + col;
-        const i16x4_t r0 = lds_tr16(b), r1 = lds_tr16(b + 4 * B3_RS);
-        return __builtin_bit_cast(f16x8_t, (i16x8_t)__builtin_shufflevector(r0, r1, 0, 1, 2, 3, 4, 5, 6, 7));
+        return frag16<f16x8_t>(S + (panel * 2 + pl) * PLANE + h * BK * B3_RS + off + col);
     };
-    auto group = [&](const f16x8_t (&a)[4], const f16x8_t (&b)[2]) {
-#pragma unroll
-        for (int x = 0; x < 4; x++)
-#pragma unroll
-            for (int y = 0; y < 2; y++)
-                acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[x], b[y], acc[x][y], 0, 0, 0);
-    };
+    auto group = [&](const f16x8_t (&a)[4], const f16x8_t (&b)[2]) { mfma_group(acc, a, b); };
     __syncthreads();
     for (uint64_t s = 0; s < nst; s++) {
         const short* cur = lds + (s & 1) * STAGE;
@@ -1361,7 +1302,7 @@ __global__ __launch_bounds__(768, 1) void k_syrk_h2s(const uint8_t* __restrict__
         if ((s & 1) && sf.due(s + 1 < nst)) sf.flush(acc);
     }
     sf.finish(acc);
-    epilogue_pi<LOCAL || RECT>(acc, tiles, n, bi, bj, accumulate, lane, wm, wn, blk);
+    epilogue_pi<LOCAL || RECT>(acc, tiles, n, bi, bj, accumulate, lane, wm, wn, wg);
     sf.release(seg);
 }
 
@@ -1539,20 +1480,20 @@ __global__ __launch_bounds__(256, 2) void k_syrk(const uint8_t* __restrict__ src
     uint64_t ldo = BM;
     const uint8_t* srcb = nullptr;
     uint64_t ldb = 0;
-    if constexpr (RECT) {  // two operands: quadrant q of block w = bj * nba + bi of the rectangle
+    if (RECT || part_tab) {
+        // quadrant q of 256-block w, written into that dense block: w = bj * nba + bi of the
+        // two-operand rectangle, or (cfg5) slot w of the part's layout
         const uint64_t w = blockIdx.x >> 2, q = blockIdx.x & 3;
-        ti = 2 * (uint32_t)(w % rb.nba) + (uint32_t)(q & 1);
-        tj = 2 * (uint32_t)(w / rb.nba) + (uint32_t)(q >> 1);
+        uint32_t bi, bj;
+        block_coords<RECT>(0, (uint32_t)w, true, part_tab, rb, bi, bj);
+        ti = 2 * bi + (uint32_t)(q & 1);
+        tj = 2 * bj + (uint32_t)(q >> 1);
         T = tiles + w * 65536 + (q & 1) * 128 * 256 + (q >> 1) * 128;
         ldo = 256;
-        srcb = rb.P;
-        ldb = rb.pitch;
-    } else if (part_tab) {  // cfg5: quadrant q of slot w of the part's layout, written into its dense block
-        const uint64_t w = blockIdx.x >> 2, q = blockIdx.x & 3;
-        ti = 2 * (part_tab[w] & 0xffffu) + (uint32_t)(q & 1);
-        tj = 2 * (part_tab[w] >> 16) + (uint32_t)(q >> 1);
-        T = tiles + w * 65536 + (q & 1) * 128 * 256 + (q >> 1) * 128;
-        ldo = 256;
+        if constexpr (RECT) {
+            srcb = rb.P;
+            ldb = rb.pitch;
+        }
     } else {
         tile_coords(blockIdx.x, ti, tj);
         T = tiles + (uint64_t)blockIdx.x * (BM * BM);
@@ -1811,27 +1752,27 @@ void launch_syrk_dense_h2(const float* Z, uint64_t ldz, uint64_t n, uint64_t m, 
     f32w::k_split_h2<false><<<(unsigned)m, 256, 0, st>>>(Z, ldz, n, nullptr, flag);
     SNPMI_HIP(hipGetLastError());
     const uint64_t C = dense_h2_chunk_snps(n);
+    const f32w::SyrkGrid whole;  // all g blocks in one slice; MODE 6 takes its order table as lut2
     for (uint64_t c0 = 0; c0 < m; c0 += C) {
         const uint64_t cnt = std::min(C, m - c0), steps = 2 * ceil_div(cnt, (uint64_t)32);
         f32w::k_image_h2<<<dim3((unsigned)nb, (unsigned)steps), 256, 0, st>>>(Z + c0 * ldz, ldz, n, cnt, (short*)img);
         SNPMI_HIP(hipGetLastError());
-        f32w::k_syrk_h2<false, 6, true><<<(unsigned)g, 512, 0, st>>>((const uint8_t*)img, ldz, n, cnt, order, flag,
-                                                                      tiles, accumulate || c0 > 0, 0, 1, 0, 0,
-                                                                      seg_ctx());
+        f32w::k_syrk_h2<false, 6, true><<<(unsigned)g, 512, 0, st>>>((const uint8_t*)img, ldz, n, cnt, order, flag, tiles,
+                                                                      accumulate || c0 > 0, whole, seg_ctx());
         SNPMI_HIP(hipGetLastError());
     }
     for_segments(m, accumulate, [&](uint64_t c0, uint64_t cnt, int acc) {
-        f32w::k_syrk256d<><<<(unsigned)g, 512, 0, st>>>(Z + c0 * ldz, ldz, n, cnt, tiles, acc, 0, 1, flag);
+        f32w::k_syrk256d<><<<(unsigned)g, 512, 0, st>>>(Z + c0 * ldz, ldz, n, cnt, tiles, acc, flag);
         SNPMI_HIP(hipGetLastError());
     });
 }
 
 // The default f32 chain, launched from this one place: the fp16x2 kernel (k_syrk_h2s, or k_syrk_h2
 // by hook "h2") and the bf16x3 kernel gated on its range flag; h2 == nullptr: the bf16x3 kernel
-// alone.  Grid x = blocks [L0, L1) of `table` (LOCAL: the part's layout table, which is also the
-// storage order; else the supertile order of the fp16x2 kernels, while the bf16x3 kernel walks the
-// triangle -- both keep their full-grid block identity through wg0 = L0).  slices > 1 (grid y):
-// slice y covers SNPs [y * kslice, + kslice) into dst + y * slice_elems.
+// alone.  All three get the same SyrkGrid: grid x = blocks [wg0, wg0 + blocks) of its table (LOCAL:
+// the part's layout table, which is also the storage order; else the supertile order of the fp16x2
+// kernels, while the bf16x3 kernel walks the triangle -- both keep their full-grid block identity
+// through wg0); slices > 1 (grid y) is its split-K, into dst + y * slice_elems.
 // MI355X, N=50k, 10k SNPs (tools/ubench.py syrk): fp16x2 with 32-SNP stages 577 TFLOP/s, 16-SNP
 // stages 505-564, bf16x3 300-313 (profiles/r01j/ubench_syrk_h2_modes.jsonl); the loader in its own
 // waves (k_syrk_h2s) 256.6 vs 270.0 ms per 50k x 62.5k launch (profiles/r06g); supertile block
@@ -1840,31 +1781,40 @@ void launch_syrk_dense_h2(const float* Z, uint64_t ldz, uint64_t n, uint64_t m, 
 // prefetched into registers: 311.0 vs 307.1 for the loader interleaved between the MFMA groups at
 // N=50k, 304.1 vs 300.5 at N=30k (profiles/r01i/ubench_syrk_bf3_mode2.jsonl).
 struct F32Chain {
-    uint64_t L0, L1;
+    f32w::SyrkGrid grid;
+    uint64_t blocks;
     unsigned slices;
-    uint64_t kslice, slice_elems;
     float* dst;
-    const uint32_t* table;
     const H2Lut* h2;
 };
+
+// one slice over the first `blocks` blocks of `table`
+static F32Chain f32_chain(uint64_t blocks, const uint32_t* table, float* dst, const H2Lut* h2) {
+    F32Chain c{};
+    c.grid.table = table;
+    c.blocks = blocks;
+    c.slices = 1;
+    c.dst = dst;
+    c.h2 = h2;
+    return c;
+}
 
 template <bool LOCAL>
 static void launch_f32_chain(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, const uint32_t* lut3,
                              const F32Chain& c, int accumulate, hipStream_t st) {
-    const dim3 grid((unsigned)(c.L1 - c.L0), c.slices);
+    const dim3 grid((unsigned)c.blocks, c.slices);
     const SegCtx seg = seg_ctx();
+    const uint32_t* gate = c.h2 ? c.h2->flag : nullptr;
     if (c.h2) {
         if (g_h2_kernel == 1)
             f32w::k_syrk_h2s<LOCAL><<<grid, 768, 0, st>>>(packed, pitch, n, m, c.h2->lut2, c.h2->flag, c.dst, accumulate,
-                                                         0, 1, c.kslice, c.slice_elems, seg, c.table, c.L0);
+                                                         c.grid, seg);
         else
             f32w::k_syrk_h2<LOCAL><<<grid, 512, 0, st>>>(packed, pitch, n, m, c.h2->lut2, c.h2->flag, c.dst, accumulate,
-                                                        0, 1, c.kslice, c.slice_elems, seg, c.table, c.L0);
+                                                        c.grid, seg);
         SNPMI_HIP(hipGetLastError());
     }
-    f32w::k_syrk_bf3<LOCAL><<<grid, 512, 0, st>>>(packed, pitch, n, m, lut3, c.dst, accumulate, 0, 1, c.kslice,
-                                                 c.slice_elems, c.h2 ? c.h2->flag : nullptr, seg, c.L0,
-                                                 LOCAL ? c.table : nullptr);
+    f32w::k_syrk_bf3<LOCAL><<<grid, 512, 0, st>>>(packed, pitch, n, m, lut3, gate, c.dst, accumulate, c.grid, seg);
     SNPMI_HIP(hipGetLastError());
 }
 
@@ -1898,13 +1848,15 @@ void launch_syrk_rect_f32(const uint8_t* Pa, uint64_t pitch_a, uint64_t n_a, con
     }
     const SegCtx seg = seg_ctx();
     const RectArg<true> rb{Pb, pitch_b, (uint32_t)ceil_div(n_a, 256), nullptr};
+    const f32w::SyrkGrid whole;  // every block of the rectangle in one launch, one slice
+    const uint32_t* gate = h2 ? h2->flag : nullptr;
     if (h2) {
         f32w::k_syrk_h2s<false, true><<<(unsigned)g, 768, 0, st>>>(Pa, pitch_a, n_a, m, h2->lut2, h2->flag, blocks,
-                                                                  accumulate, 0, 1, 0, 0, seg, nullptr, 0, rb);
+                                                                  accumulate, whole, seg, rb);
         SNPMI_HIP(hipGetLastError());
     }
-    f32w::k_syrk_bf3<false, true><<<(unsigned)g, 512, 0, st>>>(Pa, pitch_a, n_a, m, lut3, blocks, accumulate, 0, 1, 0, 0,
-                                                              h2 ? h2->flag : nullptr, seg, 0, nullptr, rb);
+    f32w::k_syrk_bf3<false, true><<<(unsigned)g, 512, 0, st>>>(Pa, pitch_a, n_a, m, lut3, gate, blocks, accumulate, whole,
+                                                              seg, rb);
     SNPMI_HIP(hipGetLastError());
 }
 
@@ -1931,10 +1883,10 @@ void launch_syrk_packed_bf3(const uint8_t* packed, uint64_t pitch, uint64_t n, u
     check_chain_pitch(pitch, n);
     if (m == 0) return zero_unless_accumulating(o, n, SNPMI_DT_F32, accumulate, st);
     if (o.tab)
-        launch_f32_chain<true>(packed, pitch, n, m, lut3, {0, o.blocks, 1, 0, 0, (float*)o.k, o.tab, h2}, accumulate, st);
+        launch_f32_chain<true>(packed, pitch, n, m, lut3, f32_chain(o.blocks, o.tab, (float*)o.k, h2), accumulate, st);
     else
         launch_f32_chain<false>(packed, pitch, n, m, lut3,
-                                {0, o.blocks, 1, 0, 0, (float*)o.k, h2 ? packed_block_order(ceil_div(n, 256)) : nullptr, h2},
+                                f32_chain(o.blocks, h2 ? packed_block_order(ceil_div(n, 256)) : nullptr, (float*)o.k, h2),
                                 accumulate, st);
 }
 
@@ -1950,8 +1902,9 @@ void launch_syrk_packed_h2_cols(const uint8_t* packed, uint64_t pitch, uint64_t 
     SNPMI_REQUIRE(h2 && L0 < L1 && L1 <= g && g < (1ull << 31), SNPMI_E_ARG, "bad SYRK column group");
     check_chain_pitch(pitch, n);
     if (m == 0) return;
-    launch_f32_chain<false>(packed, pitch, n, m, lut3, {L0, L1, 1, 0, 0, tiles, packed_block_order(nb), h2}, accumulate,
-                            st);
+    F32Chain c = f32_chain(L1 - L0, packed_block_order(nb), tiles, h2);
+    c.grid.wg0 = L0;
+    launch_f32_chain<false>(packed, pitch, n, m, lut3, c, accumulate, st);
 }
 
 // split-K form for grids too small to fill the chip (N <~ 16k): `slices` partial tile sets in
@@ -1964,8 +1917,11 @@ void launch_syrk_packed_bf3_split(const uint8_t* packed, uint64_t pitch, uint64_
     const uint64_t kslice = round_up(ceil_div(m, (uint64_t)slices), (uint64_t)2 * f32w::BK);
     const unsigned S = (unsigned)ceil_div(m, kslice);
     SNPMI_REQUIRE(g < (1ull << 31) && S >= 1, SNPMI_E_ARG, "bad split");
-    launch_f32_chain<false>(packed, pitch, n, m, lut3,
-                            {0, g, S, kslice, elems, partial, h2 ? packed_block_order(nb) : nullptr, h2}, 0, st);
+    F32Chain c = f32_chain(g, h2 ? packed_block_order(nb) : nullptr, partial, h2);
+    c.slices = S;
+    c.grid.kslice = kslice;
+    c.grid.slice_elems = elems;
+    launch_f32_chain<false>(packed, pitch, n, m, lut3, c, /*accumulate=*/0, st);
     launch_tile_reduce(partial, S, elems, tiles, accumulate, st);
 }
 
@@ -1976,9 +1932,10 @@ void launch_syrk_dense_part(const float* Z, uint64_t ldz, uint64_t n, uint64_t m
     SNPMI_REQUIRE(o.blocks < (1ull << 31), SNPMI_E_ARG, "too many GRM blocks for one launch");
     SNPMI_REQUIRE(ldz % 4 == 0 && ldz >= ceil_div(n, 256) * 256, SNPMI_E_ARG, "dense GRM operand needs ldz >= round_up(n, 256)");
     if (m == 0) return zero_unless_accumulating(o, n, SNPMI_DT_F32, accumulate, st);
+    const uint32_t* ungated = nullptr;
     for_segments(m, accumulate, [&](uint64_t c0, uint64_t cnt, int acc) {
-        f32w::k_syrk256d<true><<<(unsigned)o.blocks, 512, 0, st>>>(Z + c0 * ldz, ldz, n, cnt, (float*)o.k, acc, 0, 1,
-                                                                   nullptr, o.tab);
+        f32w::k_syrk256d<true><<<(unsigned)o.blocks, 512, 0, st>>>(Z + c0 * ldz, ldz, n, cnt, (float*)o.k, acc, ungated,
+                                                                   o.tab);
         SNPMI_HIP(hipGetLastError());
     });
 }

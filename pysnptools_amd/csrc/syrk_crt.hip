@@ -20,7 +20,7 @@
 // below the worst case), and only the first R <= kR moduli with P_R > 2 max_i sum_s q_is^2 run
 // (the SYRK workgroups of moduli >= R exit at once, k_crt's Garner stops at R).  A block whose LUT holds NaN/Inf raises a flag on the device and the f64 MFMA kernel
 // (gated on the flag) computes it instead.
-#include "snpmi_internal.hpp"
+#include "syrk_device.hpp"
 
 #include <cmath>
 
@@ -43,16 +43,6 @@ constexpr int RS = 288;    // LDS bytes per SNP row (256 iids + 32: the 8 rows o
 typedef int v2i __attribute__((ext_vector_type(2)));
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ void tile_coords(uint64_t L, uint32_t& ti, uint32_t& tj) {
-    uint64_t j = (uint64_t)((sqrt(8.0 * (double)L + 1.0) - 1.0) * 0.5);
-    while ((j + 1) * (j + 2) / 2 <= L) j++;
-    while (j * (j + 1) / 2 > L) j--;
-    tj = (uint32_t)j;
-    ti = (uint32_t)(L - j * (j + 1) / 2);
-}
-
-__device__ __forceinline__ int pi16(int p) { return 4 * (p & 3) + (p >> 2); }
 
 // ---------------------------------------------------------------- block exponent + range flag
 // ctl[0] = e (max |a| <= 2^e, 0 for an all-zero block), ctl[1] = 1 if any LUT value is NaN/Inf
@@ -266,14 +256,8 @@ __global__ __launch_bounds__(512, 1) void k_syrk_i8r(const uint8_t* __restrict__
     const uint32_t r = q - u * kR, bx = 8 * u + (w & 7);
     if (bx >= nblk) return;
     const uint32_t* lr = lutr + (uint64_t)r * mpad;
-    uint32_t bi, bj;
-    if (part_tab) {  // cfg5: slot b0 + bx of the part's layout (syrk.hip part_layout)
-        const uint32_t c = part_tab[b0 + bx];
-        bi = c & 0xffffu;
-        bj = c >> 16;
-    } else {
-        tile_coords(b0 + bx, bi, bj);
-    }
+    uint32_t bi, bj;  // part_tab (cfg5): slot b0 + bx of the part's layout (syrk.hip part_layout)
+    block_coords<false>(b0, bx, part_tab != nullptr, part_tab, RectArg<false>(), bi, bj);
     if ((int)r >= block_moduli(lgp, bi, bj, L, ctl, lgp)) return;  // this block's K_int fits the first R_b moduli
     const uint64_t i0 = (uint64_t)bi * BW, j0 = (uint64_t)bj * BW;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -405,19 +389,10 @@ __global__ __launch_bounds__(768, 1) void k_syrk_i8w(const uint8_t* __restrict__
     const uint32_t w = blockIdx.x, q = w >> 3, u = q / kR;
     const uint32_t r = q - u * kR, bx = 8 * u + (w & 7);
     if (bx >= nblk) return;
-    uint32_t bi, bj;
+    uint32_t bi, bj;  // RECT: block b0 + bx = bj * nba + bi of the rectangle
+    block_coords<RECT>(b0, bx, part_tab != nullptr, part_tab, rb, bi, bj);
     const double* lgpb = lgp;
-    if constexpr (RECT) {  // two operands: block b0 + bx = bj * nba + bi of the rectangle
-        bi = (uint32_t)((b0 + bx) % rb.nba);
-        bj = (uint32_t)((b0 + bx) / rb.nba);
-        lgpb = rb.lgp;
-    } else if (part_tab) {
-        const uint32_t c = part_tab[b0 + bx];
-        bi = c & 0xffffu;
-        bj = c >> 16;
-    } else {
-        tile_coords(b0 + bx, bi, bj);
-    }
+    if constexpr (RECT) lgpb = rb.lgp;
     if ((int)r >= block_moduli(lgp, bi, bj, L, ctl, lgpb)) return;  // this block's K_int fits the first R_b moduli
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -628,18 +603,9 @@ __global__ __launch_bounds__(256) void k_crt(const uint8_t* __restrict__ res, ui
     const int row = 4 * (blockIdx.x & 63) + (threadIdx.x >> 6), col = 4 * (threadIdx.x & 63);
     const bool part = RECT || part_tab != nullptr;  // whole dense blocks at slot b0 + blk
     uint32_t bi, bj;
+    block_coords<RECT>(b0, blk, part, part_tab, rb, bi, bj);
     const double* lgpb = lgp;
-    if constexpr (RECT) {
-        bi = (uint32_t)((b0 + blk) % rb.nba);
-        bj = (uint32_t)((b0 + blk) / rb.nba);
-        lgpb = rb.lgp;
-    } else if (part) {
-        const uint32_t c = part_tab[b0 + blk];
-        bi = c & 0xffffu;
-        bj = c >> 16;
-    } else {
-        tile_coords(b0 + blk, bi, bj);
-    }
+    if constexpr (RECT) lgpb = rb.lgp;
     const int R = block_moduli(lgp, bi, bj, L, ctl, lgpb);  // the moduli k_syrk_i8* ran for this block
     if (rec && (blockIdx.x & 63) == 0 && threadIdx.x == 0) {
         atomicAdd(rec + 2, (unsigned long long)R);
