@@ -441,6 +441,12 @@ int snpmi_grm_part_trace_f32(const float* blocks, uint64_t n_iid, int part_rank,
 int snpmi_grm_part_trace_f64(const double* blocks, uint64_t n_iid, int part_rank, int part_world, double* trace);
 /* free / total HBM of the current device (hipMemGetInfo): whether a replicated K fits */
 int snpmi_device_memory(uint64_t* free_bytes, uint64_t* total_bytes);
+/* K_tiles (+)= Z Z^T of a dense device operand: Z is [n_sid][ldz] of dtype, F order (column s, one
+ * SNP, at Z + s * ldz; its first n_iid rows are the values).  ldz % 4 == 0, and ldz >=
+ * round_up(n_iid, 256) for f32 at n_iid >= 4096, ldz >= round_up(n_iid, 128) otherwise: the kernels
+ * read whole iid panels.  Rows n_iid..ldz-1 must be readable; their contents (NaN included) never
+ * reach K[0..n_iid) and never move the fp16 range check.  K_tiles: snpmi_grm_tile_bytes(n_iid,
+ * dtype); accumulate != 0 adds to it, 0 overwrites it (n_sid == 0: zeroes it). */
 int snpmi_dev_syrk_dense(const void* Z, uint64_t ldz, uint64_t n_iid, uint64_t n_sid, int dtype,
                          void* K_tiles, int accumulate);
 /* tiles -> K[ri[r], ci[c]] (ri/ci NULL = identity), scaled by `scale` */

@@ -1092,7 +1092,9 @@ static void syrk_dense_auto(Device& d, const void* Z, uint64_t ldz, uint64_t n, 
         }
     }
     if (h2_path && n >= 4096 && ldz % 256 == 0) {
-        const uint64_t nb = ldz / 256;
+        // the blocks of n, not of ldz: the launch, the stage images and the kernel all count
+        // ceil(n / 256), and a longer ldz (allowed: rows past n are never used) must not change them
+        const uint64_t nb = ceil_div(n, 256);
         const uint64_t scratch = round_up(dense_h2_scratch_bytes(n, m), 256);
         uint16_t* img = nullptr;
         try {

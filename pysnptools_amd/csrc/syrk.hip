@@ -1727,7 +1727,8 @@ uint64_t dense_h2_scratch_bytes(uint64_t n, uint64_t m) {
     return round_up(c, 32) / 16 * nb * 2 * 9216;
 }
 
-// Dense f32 operand Z ([sid][ldz], ld = round_up(n, 256), n >= 4096) -> K tiles on the fp16 MFMA
+// Dense f32 operand Z ([sid][ldz], ldz % 256 == 0, ldz >= round_up(n, 256), n >= 4096; every block
+// count below is ceil(n / 256), whatever ldz, and so is the order table's) -> K tiles on the fp16 MFMA
 // pipe: the range check (k_split_h2<false>, column max -> flag) runs over the whole block, then
 // per SNP chunk k_image_h2 rewrites the chunk once as stage images (the exact LDS rows of the
 // packed loader, 4.6 B per value) that k_syrk_h2<MODE 6> moves into LDS by DMA; k_syrk256d (the
@@ -1739,7 +1740,7 @@ void launch_syrk_dense_h2(const float* Z, uint64_t ldz, uint64_t n, uint64_t m, 
     if (g == 0) return;
     SNPMI_REQUIRE(g < (1ull << 31) && m < (1ull << 31) && nb < 65536, SNPMI_E_ARG,
                   "too many GRM blocks / SNPs for one launch");
-    SNPMI_REQUIRE(ldz % 256 == 0 && ldz >= nb * 256, SNPMI_E_ARG, "dense GRM operand needs ldz = round_up(n, 256)");
+    SNPMI_REQUIRE(ldz % 256 == 0 && ldz >= nb * 256, SNPMI_E_ARG, "dense GRM operand needs ldz % 256 == 0, ldz >= round_up(n, 256)");
     if (m == 0) {
         if (!accumulate) SNPMI_HIP(hipMemsetAsync(tiles, 0, n_tiles_upper(n) * BM * BM * sizeof(float), st));
         return;
