@@ -254,6 +254,37 @@ int snpmi_scale_f32(float* val, uint64_t count, double scale);
 int snpmi_scale_f64(double* val, uint64_t count, double scale);
 int snpmi_diag_k_to_n_f64(double* K, uint64_t n, double* factor);
 
+/* ---------------------------------------------------------------- genotype distributions (dist.hip)
+ * A distribution array is rows x cols_total x 3 (iid, SNP, probability of 0 / 1 / 2 copies), host
+ * memory or device memory of the current device.  F order: element (i, s, k) at
+ * i + rows * s + rows * cols_total * k (three planes); C order: at (i * cols_total + s) * 3 + k.
+ * The calls below work on the SNPs [col0, col0 + cols) of it; of a host array only those slabs
+ * are uploaded, in SNP chunks of bounded scratch. */
+/* Expected values, replacing `(distdata.val * weights).sum(axis=-1)` of snpreader/_dist2snp.py:47-52:
+ * with w = {0, .5, 1} * max_weight in T, out[i, s] = ((0 + p0 w0) + p1 w1) + p2 w2 in T, bit for
+ * bit NumPy's sum (NaN when any component is; +0 when all three products are -0).  out is tight
+ * rows x cols in out_order_c. */
+int snpmi_dist_to_snp_f32(const float* dist, uint64_t rows, uint64_t cols_total, uint64_t col0, uint64_t cols,
+                          int order_c, double max_weight, float* out, int out_order_c);
+int snpmi_dist_to_snp_f64(const double* dist, uint64_t rows, uint64_t cols_total, uint64_t col0, uint64_t cols,
+                          int order_c, double max_weight, double* out, int out_order_c);
+/* One-hot distributions of SNP values, replacing _snpval_to_distval of distreader/_snp2dist.py:41-54:
+ * out[i, s, c] = 1 where (T)(val * (T)(2 / max_weight)) == c, else 0; a value that matches no c
+ * (NaN included) gives NaN in all three.  out is rows x cols x 3 in val's order. */
+int snpmi_snp_to_dist_f32(const float* val, uint64_t rows, uint64_t cols, int order_c, double max_weight, float* out);
+int snpmi_snp_to_dist_f64(const double* val, uint64_t rows, uint64_t cols, int order_c, double max_weight,
+                          double* out);
+/* Inside a GRM session of `rows` iids: expected values of the SNP range written straight into the
+ * library's dense operand, standardized there (stats [cols][2], host: read if use_stats, else
+ * written) and Z Z^T added to the session -- one block of the loop of snpreader.py:651-655 over
+ * `dist.as_snp()`, replacing its read (_dist2snp.py:47-52), standardize and `K += Z.dot(Z.T)`. */
+int snpmi_grm_add_dist_f32(const float* dist, uint64_t rows, uint64_t cols_total, uint64_t col0, uint64_t cols,
+                           int order_c, double max_weight, int std_kind, double a, double b, int use_stats,
+                           float* stats);
+int snpmi_grm_add_dist_f64(const double* dist, uint64_t rows, uint64_t cols_total, uint64_t col0, uint64_t cols,
+                           int order_c, double max_weight, int std_kind, double a, double b, int use_stats,
+                           double* stats);
+
 /* ---------------------------------------------------------------- device-resident API
  * Buffers below are device pointers from snpmi_dev_alloc; work is enqueued on the
  * library's per-device stream (use snpmi_stream_sync / events).  Packed BED data on the

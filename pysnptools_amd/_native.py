@@ -75,6 +75,12 @@ _SIGS = {
                                         _vp],
     "snpmi_grm_add_dense_f32": [_vp, _u64, _u64, _i32],
     "snpmi_grm_add_dense_f64": [_vp, _u64, _u64, _i32],
+    "snpmi_dist_to_snp_f32": [_vp, _u64, _u64, _u64, _u64, _i32, _f64, _vp, _i32],
+    "snpmi_dist_to_snp_f64": [_vp, _u64, _u64, _u64, _u64, _i32, _f64, _vp, _i32],
+    "snpmi_snp_to_dist_f32": [_vp, _u64, _u64, _i32, _f64, _vp],
+    "snpmi_snp_to_dist_f64": [_vp, _u64, _u64, _i32, _f64, _vp],
+    "snpmi_grm_add_dist_f32": [_vp, _u64, _u64, _u64, _u64, _i32, _f64, _i32, _f64, _f64, _i32, _vp],
+    "snpmi_grm_add_dist_f64": [_vp, _u64, _u64, _u64, _u64, _i32, _f64, _i32, _f64, _f64, _i32, _vp],
     "snpmi_grm_session_tiles": [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64)],
     "snpmi_grm_session_sum": [_i32, _i32, _i32],
     "snpmi_grm_end": [_i32, _dp, _vp],

@@ -145,6 +145,7 @@ void release_pinned() {
 
 // one API call at a time per process: scratch slots and the stream are shared
 static std::recursive_mutex g_call_mutex;
+std::recursive_mutex& call_mutex() { return g_call_mutex; }
 
 // ====================================================================== host helpers
 static int resolve_threads(int num_threads) {
@@ -392,7 +393,7 @@ static void chunk_done(Device& d, int slot) { SNPMI_HIP(hipEventRecord(d.consume
 // written directly, without the host staging -- the device-resident SnpData / KernelData of
 // pysnptools_amd.hbm (the reference's array-module seam, util/__init__.py:652-730).  Stats
 // arrays stay host memory.
-static bool is_device_ptr(Device& d, const void* p) {
+bool is_device_ptr(Device& d, const void* p) {
     if (!p) return false;
     hipPointerAttribute_t at;
     if (hipPointerGetAttributes(&at, p) != hipSuccess) {
@@ -1223,6 +1224,32 @@ static void grm_add_dense_impl(const T* val, uint64_t rows, uint64_t cols, int o
     uint64_t ldz = 0;
     const T* Z = dense_upload(d, val, rows, cols, order_c, &ldz);
     syrk_dense_auto(d, Z, ldz, rows, cols, DT<T>::v, tiles, g_session.wrote ? 1 : 0);
+    g_session.wrote = true;
+    SNPMI_HIP(hipStreamSynchronize(d.stream));
+}
+
+// dist.hip (snpmi_grm_add_dist_*): the session's operand buffer, and the add of a block converted
+// into it -- grm_dense_impl's standardize + SYRK on the session's tiles
+void* grm_session_operand(int dtype, uint64_t rows, uint64_t cols, uint64_t* ldz) {
+    SNPMI_REQUIRE(g_session.active, SNPMI_E_ARG, "no GRM session (call snpmi_grm_begin)");
+    SNPMI_REQUIRE(g_session.dtype == dtype, SNPMI_E_ARG, "dtype differs from snpmi_grm_begin");
+    SNPMI_REQUIRE(rows == g_session.n, SNPMI_E_ARG, "iid count differs from snpmi_grm_begin");
+    *ldz = round_up(std::max<uint64_t>(rows, 1), 256);
+    return device().get(Device::S_DENSE, *ldz * std::max<uint64_t>(cols, 1) * dtype_size(dtype));
+}
+
+void grm_session_add_operand(int dtype, void* Z, uint64_t ldz, uint64_t cols, int std_kind, double a, double b,
+                             int use_stats, void* stats) {
+    Device& d = device();
+    const uint64_t n = g_session.n;
+    if (std_kind != SNPMI_STD_NONE) {
+        const size_t sb = cols * 2 * dtype_size(dtype);
+        void* ds = d.get(Device::S_STATS, sb);
+        if (use_stats) SNPMI_HIP(hipMemcpyAsync(ds, stats, sb, hipMemcpyHostToDevice, d.stream));
+        launch_dense_standardize(Z, n, cols, ldz, 0, dtype, std_kind, a, b, use_stats, ds, d.stream);
+        if (!use_stats) SNPMI_HIP(hipMemcpyAsync(stats, ds, sb, hipMemcpyDeviceToHost, d.stream));
+    }
+    syrk_dense_auto(d, Z, ldz, n, cols, dtype, session_tiles(d), g_session.wrote ? 1 : 0);
     g_session.wrote = true;
     SNPMI_HIP(hipStreamSynchronize(d.stream));
 }

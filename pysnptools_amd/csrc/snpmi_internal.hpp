@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <cstring>
 #include <functional>
+#include <mutex>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -93,7 +94,9 @@ struct Device {
                 S_WIN, S_DPACK, S_DLUT, S_CRTREC, S_SEG, S_STDFLAG, S_DIAG,
                 // rect GRM session: blocks, the two repacked operands, per side index / plan / window, diagonal pairs
                 S_RECT, S_RECT_A, S_RECT_B, S_RECT_IDX_A, S_RECT_IDX_B, S_RECT_PLAN_A, S_RECT_PLAN_B, S_RECT_WIN_A,
-                S_RECT_WIN_B, S_RECT_PAIRS, S_NUM };
+                S_RECT_WIN_B, S_RECT_PAIRS,
+                // dist.hip: staged slabs of a host distribution array, converted block on its way out
+                S_DIST, S_DIST_OUT, S_NUM };
     void* buf[S_NUM] = {};
     // chunk pipeline events (slot = chunk parity), all on-device ordering, no host spin:
     hipEvent_t staged[2] = {};    // copy stream: H2D of pinned slot done (host may refill it)
@@ -121,6 +124,20 @@ hipStream_t stream();  // the calling thread's current stream (compute, or aux a
 // pinned host staging buffers (grow-only, per thread)
 void* pinned(int slot, size_t bytes);
 void release_pinned();
+
+// ------------------------------------------------------------------ api.hip services for dist.hip
+// one API call at a time per process (scratch slots and the stream are shared): every entry point
+// that touches them holds this lock
+std::recursive_mutex& call_mutex();
+// true for a pointer into device memory of the current device (SNPMI_E_ARG for another device's)
+bool is_device_ptr(Device& d, const void* p);
+// The open GRM session's F-order dense operand buffer for `cols` SNPs of its n iids (checks the
+// session, dtype and n; *ldz = round_up(n, 256), which meets snpmi_dev_syrk_dense's contract), and
+// the add of a block written there: in-place standardize (host stats [cols][2], read if use_stats,
+// else written), Z Z^T into the session's tiles, session marked written.  Callers hold call_mutex.
+void* grm_session_operand(int dtype, uint64_t rows, uint64_t cols, uint64_t* ldz);
+void grm_session_add_operand(int dtype, void* Z, uint64_t ldz, uint64_t cols, int std_kind, double a, double b,
+                             int use_stats, void* stats);
 
 // ------------------------------------------------------------------ kernel launchers (kernels.hip)
 // The tuning / test hooks of snpmi_set_kernel_variant live beside the code that reads them; api.hip's

@@ -1,0 +1,150 @@
+"""``distreader.as_snp()``: expected SNP values of genotype distributions (reference snpreader/_dist2snp.py).
+
+The conversion ``(val * weights).sum(axis=-1)`` (_dist2snp.py:47-52) runs as ``snpmi_dist_to_snp_*``,
+bit for bit NumPy's result.  Over stored or in-memory distributions (DistData, DistMemMap, DistNpz)
+with every iid and a contiguous ascending SNP range the kernel reads that range of the base array
+in place -- only those slabs of a host array are uploaded, nothing of an HBM-resident one moves;
+any other selection is gathered first (the 3-D ``sub_matrix`` path) and converted whole.
+"""
+import numpy as np
+
+from pysnptools_amd import _native as N
+from pysnptools_amd.snpreader.snpreader import SnpReader
+
+
+def _order_c(val):
+    return 1 if (val.flags["C_CONTIGUOUS"] and not val.flags["F_CONTIGUOUS"]) else 0
+
+
+def _contiguous(val):
+    """``val`` itself when C- or F-contiguous (NumPy or HbmArray), else a C-contiguous host copy."""
+    if val.flags["C_CONTIGUOUS"] or val.flags["F_CONTIGUOUS"]:
+        return val
+    return np.ascontiguousarray(val)
+
+
+def dist_to_snp(val, col0, cols, max_weight, order, to_hbm=False):
+    """Expected values of SNPs [col0, col0 + cols) of the iid x sid x 3 array ``val`` (NumPy or
+    HbmArray, float32 / float64) as a new iid x cols array of the same dtype; order 'A' follows
+    ``val``.  The result is an HbmArray when ``val`` is one or ``to_hbm``."""
+    from pysnptools_amd import hbm
+
+    val = _contiguous(val)
+    rows, cols_total = int(val.shape[0]), int(val.shape[1])
+    src_c = _order_c(val)
+    if order == "A":
+        order = "C" if src_c else "F"
+    on_dev = to_hbm or isinstance(val, hbm.HbmArray)
+    out = (hbm.empty if on_dev else np.empty)((rows, cols), dtype=val.dtype, order=order)
+    if rows and cols:
+        N.call("snpmi_dist_to_snp_" + N.suffix(val.dtype), N.ptr(val), rows, cols_total, int(col0), int(cols), src_c,
+               float(max_weight), N.ptr(out), 1 if order == "C" else 0)
+    return out
+
+
+def _stored_range(distreader, dtype):
+    """(base array, col0, cols) when ``distreader`` is a DistData / DistMemMap / DistNpz, or a
+    subset of one with every iid in order and a contiguous ascending SNP range, whose values have
+    ``dtype``; else None."""
+    from pysnptools_amd.distreader.distdata import DistData
+    from pysnptools_amd.distreader.distnpz import DistNpz
+    from pysnptools_amd.snpreader.snpreader import _resolve
+
+    base, rows, cols = _resolve(distreader)
+    if not isinstance(base, (DistData, DistNpz)):
+        return None
+    if rows is not None and not np.array_equal(rows, np.arange(base.iid_count)):
+        return None
+    if cols is None:
+        col0, count = 0, base.sid_count
+    else:
+        cols = np.asarray(cols, dtype=np.int64)
+        if len(cols) and not np.array_equal(cols, np.arange(cols[0], cols[0] + len(cols))):
+            return None
+        col0, count = (int(cols[0]) if len(cols) else 0), len(cols)
+    val = base._load_val() if isinstance(base, DistNpz) else base.val
+    if not (val.flags["C_CONTIGUOUS"] or val.flags["F_CONTIGUOUS"]):
+        return None
+    if count and val.dtype != np.dtype(dtype):  # (an empty range reads nothing: any dtype will do)
+        return None
+    return val, col0, count
+
+
+class _Dist2Snp(SnpReader):
+    def __init__(self, distreader, max_weight=2.0, block_size=None):
+        super(_Dist2Snp, self).__init__()
+        self.distreader = distreader
+        self.max_weight = float(max_weight)  # a Python float: the weights stay in the value dtype
+        self.block_size = block_size
+
+    @property
+    def row(self):
+        return self.distreader.iid
+
+    @property
+    def col(self):
+        return self.distreader.col
+
+    @property
+    def sid(self):
+        return self.distreader.sid
+
+    @property
+    def sid_count(self):
+        return self.distreader.sid_count
+
+    @property
+    def pos(self):
+        return self.distreader.pos
+
+    @property
+    def col_property(self):
+        return self.distreader.pos
+
+    def __repr__(self):
+        return "{0}.as_snp({1})".format(self.distreader,
+                                        "" if self.block_size is None else "block_size={0}".format(self.block_size))
+
+    def copyinputs(self, copier):
+        copier.input(self.distreader)
+
+    def __getitem__(self, iid_indexer_and_snp_indexer):
+        # the selection is pushed down onto the distributions (_dist2snp.py:81-83)
+        iid_indexer, snp_indexer = iid_indexer_and_snp_indexer
+        return _Dist2Snp(self.distreader[iid_indexer, snp_indexer], max_weight=self.max_weight,
+                         block_size=self.block_size)
+
+    def _read(self, row_index_or_none, col_index_or_none, order, dtype, force_python_only, view_ok, num_threads):
+        assert row_index_or_none is None and col_index_or_none is None  # indexing is pushed to the distreader
+        return self._convert(order, dtype, force_python_only, num_threads, to_hbm=False)
+
+    def _convert(self, order, dtype, force_python_only, num_threads, to_hbm):
+        from pysnptools_amd import hbm
+        from pysnptools_amd.distreader.distreader import DistReader
+        from pysnptools_amd.util import _on_device, asnumpy
+
+        dtype = np.dtype(dtype)
+        if dtype not in (np.float32, np.float64):
+            raise ValueError("dtype '{0}' not supported; use float32 or float64".format(dtype))
+        to_hbm = to_hbm or _on_device()
+        if self.iid_count == 0 or self.sid_count == 0:
+            return (hbm.empty if to_hbm else np.empty)((self.iid_count, self.sid_count), dtype=dtype,
+                                                       order="F" if order == "A" else order)
+        stored = _stored_range(self.distreader, dtype)
+        if stored is not None:
+            val, col0, cols = stored
+            return dist_to_snp(val, col0, cols, self.max_weight, order, to_hbm=to_hbm)
+        # all at once unless the SNPs outnumber both the block and the iids (_dist2snp.py:49-50)
+        if self.block_size is None or self.sid_count <= self.block_size or self.sid_count <= self.iid_count:
+            distdata = DistReader._as_distdata(self.distreader, dtype=dtype, order=order,
+                                               force_python_only=force_python_only, num_threads=num_threads)
+            return dist_to_snp(distdata.val, 0, distdata.sid_count, self.max_weight, order, to_hbm=to_hbm)
+        order = "F" if order == "A" else order
+        out = np.zeros([self.iid_count, self.sid_count], dtype=dtype, order=order)
+        for start in range(0, self.sid_count, self.block_size):
+            distdata = self.distreader[:, start:start + self.block_size].read(order=order, dtype=dtype,
+                                                                              force_python_only=force_python_only,
+                                                                              view_ok=True, num_threads=num_threads)
+            out[:, start:start + distdata.sid_count] = asnumpy(
+                dist_to_snp(distdata.val, 0, distdata.sid_count, self.max_weight, order))
+        return hbm.asarray(out, order=order) if to_hbm else out
