@@ -24,6 +24,7 @@ import os
 
 import numpy as np
 
+from pysnptools_amd import _grm as G
 from pysnptools_amd import _native as N
 
 
@@ -193,58 +194,33 @@ def read_kernel_checkpointed(reader, standardizer, path, block_size=10000, every
     one; ``standardizer`` Unit / Beta / their trained forms / Identity.  Returns
     (KernelData, trained standardizer)."""
     from pysnptools_amd.kernelreader import KernelData
-    from pysnptools_amd.snpreader.bed import Bed
-    from pysnptools_amd.snpreader.snpreader import _resolve, _trained_from
-    from pysnptools_amd.standardizer.standardizer import _std_args
-    from pysnptools_amd.util import get_num_threads
 
-    dtype = np.dtype(dtype)
-    if dtype not in (np.float32, np.float64):
-        raise ValueError("GRM dtype must be float32 or float64")
-    args = _std_args(standardizer)
-    if args is None:
+    G.require_float(dtype)
+    p = G.plan(reader, standardizer, dtype)
+    if p is None:
         raise ValueError("read_kernel_checkpointed supports Unit/Beta/UnitTrained/BetaTrained/Identity")
-    kind, a, b, use_stats, _, _ = args
     assert block_size >= 1 and every >= 1
-    base, rows, cols = _resolve(reader)
-    if not isinstance(base, Bed):
+    if p.source != G.BED:
         raise ValueError("read_kernel_checkpointed reads a Bed (or a subset of one)")
-    base._run_once()
-    n, m = reader.iid_count, reader.sid_count
-    sid = reader.sid
-    stats_in = np.ascontiguousarray(standardizer.stats_for(sid), dtype=dtype) if use_stats else None
-    meta = _fingerprint(base.filename, n, m, dtype, block_size, kind, a, b, use_stats, rows, cols, base.count_A1,
-                        stats_in)
-    col_index = np.arange(base.sid_count, dtype=np.uint64) if cols is None else np.asarray(cols, dtype=np.uint64)
-    ri = N.index_array(rows)
-    sfx = N.suffix(dtype)
-    threads = get_num_threads(num_threads if num_threads is not None else base._num_threads)
+    p.base._run_once()
+    n, m, dtype = p.n, p.m, p.dtype
+    stats_in = p.stats() if p.use_stats else None
+    meta = _fingerprint(p.base.filename, n, m, dtype, block_size, p.kind, p.a, p.b, p.use_stats, p.rows, p.cols,
+                        p.base.count_A1, stats_in)
+    threads = p.threads(num_threads)
     nblocks = (m + block_size - 1) // block_size
     K = np.empty((n, n), dtype=dtype)
-    N.call("snpmi_grm_begin", n, N.dt_code(dtype))
-    done = False
-    try:
-        stats = stats_in.copy() if use_stats else np.zeros((m, 2), dtype=dtype)
+    with G.session(n, dtype, K) as s:
+        stats = stats_in.copy() if p.use_stats else np.zeros((m, 2), dtype=dtype)
         got = _restore(path, meta, dtype)
         start = 0
         if got is not None:
             start, stats = got
         for k in range(start, nblocks):
-            s0 = k * block_size
-            ci = np.ascontiguousarray(col_index[s0:s0 + block_size])
-            pst = np.ascontiguousarray(stats[s0:s0 + len(ci)])
-            N.call("snpmi_grm_add_bed_" + sfx, base.filename.encode(), base.iid_count, base.sid_count,
-                   int(bool(base.count_A1)), N.ptr(ri), n, N.ptr(ci), len(ci), kind, a, b, int(use_stats),
-                   N.ptr(pst), threads)
-            if not use_stats:
-                stats[s0:s0 + len(ci)] = pst
+            G.feed_bed(s, p, stats, threads, slice(k * block_size, (k + 1) * block_size))
             if (k + 1) % every == 0 and k + 1 < nblocks:
                 _save(path, meta, k + 1, stats, dtype)
             if _stop_after is not None and k + 1 >= _stop_after:
                 raise _Interrupted("stopped after %d blocks (test hook)" % (k + 1))
-        done = True
-    finally:
-        N.call("snpmi_grm_end", 0, None, N.ptr(K))
-    if done:
-        _remove_all(path)
-    return KernelData(iid=reader.iid, val=K), _trained_from(standardizer, kind, a, b, sid, stats)
+    _remove_all(path)
+    return KernelData(iid=reader.iid, val=K), p.trained(stats)

@@ -76,12 +76,11 @@ class _Snp2Dist(DistReader):
     def _values(self, reader, order, dtype, force_python_only, num_threads):
         """``reader``'s values in ``order``: decoded straight into HBM when it is file- or
         generator-backed (Bed, SnpGen), else as the reference reads them."""
-        from pysnptools_amd.snpreader.bed import Bed
-        from pysnptools_amd.snpreader.snpreader import SnpReader, _is_snpgen, _resolve
+        from pysnptools_amd import _grm as G
+        from pysnptools_amd.snpreader.snpreader import SnpReader, _resolve
         from pysnptools_amd.standardizer import Identity
 
-        base, _, _ = _resolve(reader)
-        if not force_python_only and (isinstance(base, Bed) or _is_snpgen(base)):
+        if not force_python_only and G.source_kind(*_resolve(reader)[:2]) in (G.BED, G.SNPGEN, G.SNPGEN_IIDS):
             return reader.read(order=order, dtype=dtype, num_threads=num_threads, xp="hbm").val
         snpdata, _ = SnpReader._as_snpdata(reader, dtype=dtype, order=order, force_python_only=force_python_only,
                                            standardizer=Identity(), num_threads=num_threads)

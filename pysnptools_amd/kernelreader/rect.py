@@ -10,6 +10,7 @@ import os
 
 import numpy as np
 
+from pysnptools_amd import _grm as G
 from pysnptools_amd import _native as N
 
 _MODES = ("auto", "always", "never")
@@ -58,23 +59,17 @@ def use_rect(n, n_r, n_c, dtype, world, free_bytes, mode=None):
     return whole > 0.8 * free_bytes and rect <= 0.8 * free_bytes
 
 
-def rect_source(snpreader, standardizer, dtype):
-    """(base, rows, cols, std_args) when the direct path can serve this reader / standardizer /
-    dtype -- a Bed (or subsets of one), or an all-iid SnpGen, with a standardizer the fused GPU
-    path knows -- else None."""
-    from pysnptools_amd.snpreader.bed import Bed
-    from pysnptools_amd.snpreader.snpreader import _is_snpgen, _resolve
-    from pysnptools_amd.standardizer.standardizer import _std_args
+def _rect_plan(snpreader, standardizer, dtype):
+    """The GRM plan when the direct path can serve this reader / standardizer / dtype -- a Bed (or
+    subsets of one), or an all-iid SnpGen, with a standardizer the fused GPU path knows -- else None."""
+    p = G.plan(snpreader, standardizer, dtype)
+    return p if p is not None and p.source in (G.BED, G.SNPGEN) else None
 
-    if np.dtype(dtype) not in (np.float32, np.float64):
-        return None
-    args = _std_args(standardizer)
-    if args is None:
-        return None
-    base, rows, cols = _resolve(snpreader)
-    if isinstance(base, Bed) or (_is_snpgen(base) and rows is None):
-        return base, rows, cols, args
-    return None
+
+def rect_source(snpreader, standardizer, dtype):
+    """(base, rows, cols, std_args) of ``_rect_plan``, or None."""
+    p = _rect_plan(snpreader, standardizer, dtype)
+    return None if p is None else (p.base, p.rows, p.cols, p.args)
 
 
 def diag_pairs(row_index, col_index, n_rows=None, n_cols=None):
@@ -103,7 +98,6 @@ def read_rect(snpreader, standardizer, row_index, col_index, order, dtype, num_t
     when the path does not apply or ``set_grm_rect`` routes the call to the whole K."""
     from pysnptools_amd import dist as dist_mod
     from pysnptools_amd import hbm
-    from pysnptools_amd.snpreader.snpreader import _is_snpgen, _snpgen_cols
     from pysnptools_amd.util import _on_device, get_num_threads
 
     dtype = np.dtype(dtype)
@@ -114,44 +108,23 @@ def read_rect(snpreader, standardizer, row_index, col_index, order, dtype, num_t
     world = group.world if group is not None else 1
     if world > 1:
         return None
-    src = rect_source(snpreader, standardizer, dtype)
-    if src is None:
+    p = _rect_plan(snpreader, standardizer, dtype)
+    if p is None:
         return None
-    base, rows, cols, (kind, a, b, use_stats, _, _) = src
-    n = snpreader.iid_count
+    n = p.n
     ri = None if row_index is None else N.index_array(np.arange(n)[row_index])
     ci = None if col_index is None else N.index_array(np.arange(n)[col_index])
     n_r = n if ri is None else len(ri)
     n_c = n if ci is None else len(ci)
     if mode == "auto" and not use_rect(n, n_r, n_c, dtype, world, _free_bytes(), mode):
         return None
-    sid = snpreader.sid
-    stats = (np.ascontiguousarray(standardizer.stats_for(sid), dtype=dtype) if use_stats
-             else np.empty((len(sid), 2), dtype=dtype))
+    stats = p.stats()
     order = "C" if order not in ("C", "F") else order
     K = (hbm.empty if _on_device() else np.empty)((n_r, n_c), dtype=dtype, order=order)
-    sfx = N.suffix(dtype)
-    N.call("snpmi_grm_rect_begin", n_r, n_c, N.dt_code(dtype))
-    ok = False
-    try:
-        if _is_snpgen(base):
-            col_list = _snpgen_cols(base, cols)
-            base._check_seeds(col_list)
-            pitch = int(N.lib().snpmi_packed_pitch(n))
-            bs = int(base._block_size)
-            step = max(bs, (1 << 30) // pitch // bs * bs)  # the chunks of _snpgen_grm
-            for c0 in range(0, len(col_list), step):
-                here = slice(c0, min(c0 + step, len(col_list)))
-                packed, _ = base._packed(col_list[here])
-                st = np.ascontiguousarray(stats[here])
-                N.call("snpmi_grm_rect_add_packed_" + sfx, N.ptr(packed), pitch, n, here.stop - here.start, 0, kind, a,
-                       b, int(use_stats), N.ptr(st), N.ptr(ri), N.ptr(ci))
+    with G.session(n, dtype, K, rect=(ri, ci), order=order) as s:
+        if p.source == G.SNPGEN:
+            p.base._check_seeds(p.col_index())
+            G.feed_snpgen(s, p, stats)
         else:
-            base._run_once()
-            N.call("snpmi_grm_rect_add_bed_" + sfx, base.filename.encode(), base.iid_count, base.sid_count,
-                   int(bool(base.count_A1)), N.ptr(N.index_array(rows)), n, N.ptr(N.index_array(cols)), len(sid), kind,
-                   a, b, int(use_stats), N.ptr(stats), get_num_threads(num_threads), N.ptr(ri), N.ptr(ci))
-        ok = True
-    finally:
-        N.call("snpmi_grm_rect_end", 1.0, 1 if order == "C" else 0, N.ptr(K) if ok else None)
+            G.feed_bed(s, p, stats, get_num_threads(num_threads))
     return K

@@ -8,6 +8,7 @@ import logging
 
 import numpy as np
 
+from pysnptools_amd import _grm as G
 from pysnptools_amd.kernelreader.kerneldata import KernelData
 from pysnptools_amd.kernelreader.kernelreader import KernelReader
 from pysnptools_amd.kernelstandardizer import DiagKtoN
@@ -54,9 +55,6 @@ class SnpKernel(KernelReader):
         from pysnptools_amd import dist as dist_mod
         from pysnptools_amd.kernelreader.partitionedkernel import (PartitionedKernel, grm_partition_mode,
                                                                    use_partitioned)
-        from pysnptools_amd.snpreader.bed import Bed
-        from pysnptools_amd.snpreader.snpreader import _resolve
-        from pysnptools_amd.standardizer.standardizer import _std_args
 
         dtype = np.dtype(dtype)
         group = dist_mod.current()
@@ -64,10 +62,10 @@ class SnpKernel(KernelReader):
         cache = self.__dict__.setdefault("_pk", {})
         if key in cache:
             return cache[key]
-        if dtype not in (np.float32, np.float64) or _std_args(self.standardizer) is None:
+        p = G.plan(self.snpreader, self.standardizer, dtype)
+        if p is None:
             return None
-        if not isinstance(_resolve(self.snpreader)[0], Bed) or not use_partitioned(self.snpreader.iid_count, dtype,
-                                                                                   group):
+        if p.source != G.BED or not use_partitioned(p.n, dtype, group):
             cache[key] = None
             return None
         from pysnptools_amd import shard

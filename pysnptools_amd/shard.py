@@ -25,6 +25,8 @@ import ctypes
 
 import numpy as np
 
+from pysnptools_amd import _grm as G
+
 COLLECTIVES = ("reduce", "allreduce", "none")
 
 
@@ -90,8 +92,7 @@ class ShardedGrm(object):
         if collective not in COLLECTIVES:
             raise ValueError("collective must be one of %s" % (COLLECTIVES,))
         self.N, self.n, self.dtype = N, int(n), np.dtype(dtype)
-        if self.dtype not in (np.float32, np.float64):
-            raise ValueError("GRM dtype must be float32 or float64")
+        G.require_float(self.dtype)
         self.dist, self.collective, self.root = dist, collective, int(root)
         self.world = int(world) if world is not None else (dist.world if dist is not None else 1)
         self.rank = int(rank) if rank is not None else (dist.rank if dist is not None else 0)
@@ -109,13 +110,9 @@ class ShardedGrm(object):
         through the fused decode -> standardize -> SYRK; ``stats`` [len(sid_index), 2] in/out."""
         from pysnptools_amd.util import get_num_threads
 
-        N = self.N
-        ri, ci = N.index_array(iid_index), N.index_array(sid_index)
-        if len(ci) == 0:
-            return
-        N.call("snpmi_grm_add_bed_" + N.suffix(self.dtype), bed.filename.encode(), bed.iid_count, bed.sid_count,
-               int(bool(bed.count_A1)), N.ptr(ri), self.n, N.ptr(ci), len(ci), kind, a, b, int(use_stats),
-               N.ptr(stats), get_num_threads(num_threads))
+        if len(sid_index):
+            G.Session(self.n, self.dtype).add_bed(bed, iid_index, sid_index, (kind, a, b, int(use_stats)), stats,
+                                                  get_num_threads(num_threads))
 
     def add_bed_combine(self, bed, iid_index, sid_index, kind, a, b, use_stats, stats, num_threads=None, parts=2):
         """``add_bed`` of this rank's LAST SNPs + ``combine``, overlapped under a real RCCL
@@ -230,44 +227,31 @@ def grm_sharded(reader, standardizer, rank=None, world=None, dtype=np.float32, c
     then the partial K tiles are combined by ``collective`` (see ``ShardedGrm``).  Returns
     (K, trained standardizer, DiagKtoN factor or NaN): K is None on non-root ranks of a "reduce";
     with "none" K is this rank's partial sum and the stats cover only its SNPs (zeros elsewhere)."""
-    from pysnptools_amd.snpreader.bed import Bed
-    from pysnptools_amd.snpreader.snpreader import _resolve, _trained_from
-    from pysnptools_amd.standardizer.standardizer import _std_args
-
     d, rank, world = _layout(dist, rank, world)
-    dtype = np.dtype(dtype)
-    args = _std_args(standardizer)
-    if args is None:
+    G.require_float(dtype)
+    p = G.plan(reader, standardizer, dtype)
+    if p is None:
         raise ValueError("grm_sharded supports Unit/Beta/UnitTrained/BetaTrained/Identity")
     if collective == "none" and diag_k_to_n:
         raise ValueError("DiagKtoN needs the combined K (collective 'reduce' or 'allreduce')")
-    kind, a, b, use_stats, _, _ = args
-    base, rows, cols = _resolve(reader)
-    if not isinstance(base, Bed):
+    if p.source != G.BED:
         raise ValueError("grm_sharded streams a Bed (or a subset of one); DistributedBed: grm_pieces")
-    base._run_once()
-    sid = reader.sid
-    n, m = reader.iid_count, len(sid)
-    lo, hi = rank_span(m, rank, world)
-    col_index = np.arange(base.sid_count, dtype=np.uint64) if cols is None else np.asarray(cols, dtype=np.uint64)
-    if use_stats:
-        stats = np.ascontiguousarray(standardizer.stats_for(sid), dtype=dtype)
-        mine = np.ascontiguousarray(stats[lo:hi])
-    else:
-        stats = np.zeros((m, 2), dtype=dtype)
-        mine = np.zeros((hi - lo, 2), dtype=dtype)
-    g = ShardedGrm(n, dtype, d, collective, root, rank, world)
+    p.base._run_once()
+    lo, hi = rank_span(p.m, rank, world)
+    stats = p.stats(zeros=True)
+    mine = np.ascontiguousarray(stats[lo:hi])
+    g = ShardedGrm(p.n, p.dtype, d, collective, root, rank, world)
     try:
-        g.add_bed_combine(base, rows, col_index[lo:hi], kind, a, b, use_stats, mine,
-                          num_threads if num_threads is not None else base._num_threads)
-        if kind != 0 and not use_stats:
+        g.add_bed_combine(p.base, p.rows, p.col_index(np.uint64)[lo:hi], *p.std, mine,
+                          num_threads if num_threads is not None else p.base._num_threads)
+        if p.kind != 0 and not p.use_stats:
             stats[lo:hi] = mine
             stats = _sum_stats(d, stats, collective, world)
         K, factor = g.finish(out, diag_k_to_n)
     except BaseException:
         g.abort()
         raise
-    return K, _trained_from(standardizer, kind, a, b, sid, stats), factor
+    return K, p.trained(stats), factor
 
 
 def grm_pieces(reader, standardizer, rank=None, world=None, dtype="float32", diag_k_to_n=False, num_threads=None,
@@ -277,33 +261,24 @@ def grm_pieces(reader, standardizer, rank=None, world=None, dtype="float32", dia
     the ranks (default all-reduce: every rank extracts K, with DiagKtoN if asked).  The per-SNP
     stats are summed the same way (zeros for SNPs a rank did not own).
     Returns (K, trained standardizer, DiagKtoN factor or NaN)."""
-    from pysnptools_amd.snpreader.snpreader import _add_pieces, _bed_pieces, _resolve, _trained_from
-    from pysnptools_amd.standardizer.standardizer import _std_args
-
     d, rank, world = _layout(dist, rank, world)
-    dtype = np.dtype(dtype)
-    args = _std_args(standardizer)
-    assert args is not None, "grm_pieces supports Unit/Beta/UnitTrained/BetaTrained/Identity"
-    kind, a, b, use_stats, _, _ = args
-    base, rows, cols = _resolve(reader)
-    merged = _bed_pieces(base)
-    assert merged is not None, "grm_pieces needs a DistributedBed or a _MergeSIDs of Beds"
-    sid = reader.sid
-    n = reader.iid_count
-    stats = (np.ascontiguousarray(standardizer.stats_for(sid), dtype=dtype) if use_stats
-             else np.zeros((len(sid), 2), dtype=dtype))
-    mine = set(rank_pieces(merged.col_count_list, rank, world))
-    g = ShardedGrm(n, dtype, d, collective, root, rank, world)
+    G.require_float(dtype)
+    p = G.plan(reader, standardizer, dtype)
+    assert p is not None, "grm_pieces supports Unit/Beta/UnitTrained/BetaTrained/Identity"
+    assert p.source == G.PIECES, "grm_pieces needs a DistributedBed or a _MergeSIDs of Beds"
+    stats = p.stats(zeros=True)
+    mine = set(rank_pieces(p.src.col_count_list, rank, world))
+    g = ShardedGrm(p.n, p.dtype, d, collective, root, rank, world)
     try:
-        _add_pieces(merged, rows, cols, n, kind, a, b, use_stats, stats, dtype, num_threads, only=mine)
+        G.feed_pieces(G.Session(p.n, p.dtype), p, stats, num_threads, only=mine)  # into g's session
         g.combine()
-        if kind != 0 and not use_stats:
+        if p.kind != 0 and not p.use_stats:
             stats = _sum_stats(d, stats, collective, world)
         K, factor = g.finish(out, diag_k_to_n)
     except BaseException:
         g.abort()
         raise
-    return K, _trained_from(standardizer, kind, a, b, sid, stats), factor
+    return K, p.trained(stats), factor
 
 
 def part_coords(n, part, parts):
@@ -380,8 +355,7 @@ class PartitionedGrm(object):
 
         self.N = N
         self.dtype = np.dtype(dtype)
-        if self.dtype not in (np.float32, np.float64):
-            raise ValueError("GRM dtype must be float32 or float64")
+        G.require_float(self.dtype)
         self.dist = dist
         self.world = dist.world if dist is not None else 1
         self.rank = dist.rank if dist is not None else 0
@@ -604,32 +578,21 @@ def grm_partitioned(reader, standardizer, rank=None, world=None, out=None, num_t
     standardizer).  Entries of a block beyond iid n-1 are padding."""
     from pysnptools_amd import _native as N
     from pysnptools_amd import dist as dist_mod
-    from pysnptools_amd.snpreader.bed import Bed
-    from pysnptools_amd.snpreader.snpreader import _resolve, _trained_from
-    from pysnptools_amd.standardizer.standardizer import _std_args
-    from pysnptools_amd.util import get_num_threads
-
-    args = _std_args(standardizer)
-    assert args is not None, "grm_partitioned supports Unit/Beta/UnitTrained/BetaTrained/Identity"
-    kind, a, b, use_stats, _, _ = args
-    base, rows, cols = _resolve(reader)
-    assert isinstance(base, Bed), "grm_partitioned streams a Bed file"
+    G.require_float(dtype)
+    p = G.plan(reader, standardizer, dtype)
+    assert p is not None, "grm_partitioned supports Unit/Beta/UnitTrained/BetaTrained/Identity"
+    assert p.source == G.BED, "grm_partitioned streams a Bed file"
+    base, rows, cols, n, dtype = p.base, p.rows, p.cols, p.n, p.dtype
     base._run_once()
-    sid = reader.sid
-    n = reader.iid_count
-    dtype = np.dtype(dtype)
-    if dtype not in (np.float32, np.float64):
-        raise ValueError("GRM dtype must be float32 or float64")
-    stats = (np.ascontiguousarray(standardizer.stats_for(sid), dtype=dtype) if use_stats
-             else np.empty((len(sid), 2), dtype=dtype))
+    stats = p.stats()
     d = dist if dist is not None else dist_mod.current()
-    threads = get_num_threads(num_threads if num_threads is not None else base._num_threads)
+    threads = p.threads(num_threads)
     if d is not None and d.world > 1:
         if (rank is not None and rank != d.rank) or (world is not None and world != d.world):
             raise ValueError("rank/world %s/%s differ from the process group's %d/%d" % (rank, world, d.rank, d.world))
-        blocks, coords, stats = _partitioned_bed(base, rows, cols, kind, a, b, use_stats, stats, d, d.rank, d.world,
+        blocks, coords, stats = _partitioned_bed(base, rows, cols, *p.args[:4], stats, d, d.rank, d.world,
                                                  block_size, out, threads, dtype)
-        return blocks, coords, _trained_from(standardizer, kind, a, b, sid, stats)
+        return blocks, coords, p.trained(stats)
     rank = 0 if rank is None else int(rank)
     world = 1 if world is None else int(world)
     nloc = N.lib().snpmi_grm_part_blocks(n, rank, world)
@@ -642,10 +605,10 @@ def grm_partitioned(reader, standardizer, rank=None, world=None, out=None, num_t
     assert tuple(out.shape) == (nloc, 256, 256) and np.dtype(out.dtype) == dtype
     assert getattr(out, "order", None) == "C" if hasattr(out, "snpmi_ptr") else out.flags["C_CONTIGUOUS"]
     ri, ci = N.index_array(rows), N.index_array(cols)
-    N.call("snpmi_grm_part_bed_" + N.suffix(dtype), base.filename.encode(), base.iid_count, base.sid_count,
-           int(bool(base.count_A1)), N.ptr(ri), n, N.ptr(ci), len(sid), kind, a, b, int(use_stats), N.ptr(stats),
-           rank, world, N.ptr(out), threads)
-    return out, part_coords(n, rank, world), _trained_from(standardizer, kind, a, b, sid, stats)
+    N.call("snpmi_grm_part_bed_" + p.sfx, base.filename.encode(), base.iid_count, base.sid_count,
+           int(bool(base.count_A1)), N.ptr(ri), n, N.ptr(ci), p.m, *p.std, N.ptr(stats), rank, world, N.ptr(out),
+           threads)
+    return out, part_coords(n, rank, world), p.trained(stats)
 
 
 def assemble_partitioned(parts, n):

@@ -9,11 +9,8 @@ any other selection is gathered first (the 3-D ``sub_matrix`` path) and converte
 import numpy as np
 
 from pysnptools_amd import _native as N
+from pysnptools_amd._grm import order_c as _order_c
 from pysnptools_amd.snpreader.snpreader import SnpReader
-
-
-def _order_c(val):
-    return 1 if (val.flags["C_CONTIGUOUS"] and not val.flags["F_CONTIGUOUS"]) else 0
 
 
 def _contiguous(val):

@@ -22,7 +22,9 @@ import warnings
 
 import numpy as np
 
+from pysnptools_amd import _grm as G
 from pysnptools_amd import _native as N
+from pysnptools_amd._grm import feed_snpgen as _snpgen_grm  # (its one default is the chunk size)
 from pysnptools_amd.pstreader import PstReader
 from pysnptools_amd.util import get_num_threads
 
@@ -162,17 +164,14 @@ class SnpReader(PstReader):
         from pysnptools_amd.util import _on_device
 
         n = self.iid_count
-        if dtype not in (np.float32, np.float64):
-            raise ValueError("GRM dtype must be float32 or float64")
-        sfx = N.suffix(dtype)
+        G.require_float(dtype)
         # all at once unless the SNPs outnumber both the block and the iids (snpreader.py:629)
         whole = block_size is None or self.sid_count <= block_size or self.sid_count <= self.iid_count
         bs = self.sid_count if whole else block_size
         # K on xp (snpreader.py:638-643): in HBM when the values are or ARRAY_MODULE=hbm
         K = (hbm.empty if _on_device(getattr(self, "val", None)) else np.empty)((n, n), dtype=dtype)
         trained_list = []
-        N.call("snpmi_grm_begin", n, N.dt_code(dtype))
-        try:
+        with G.session(n, dtype, K) as s:
             for start in range(0, self.sid_count, max(bs, 1)):
                 reader = self if (start == 0 and bs >= self.sid_count) else self[:, start:start + bs]
                 data, trained = SnpReader._as_snpdata(reader, standardizer, force_python_only, "A", dtype,
@@ -181,10 +180,7 @@ class SnpReader(PstReader):
                 val = data.val
                 if not (val.flags["C_CONTIGUOUS"] or val.flags["F_CONTIGUOUS"]):  # (never an HbmArray)
                     val = np.asfortranarray(val)
-                order_c = 1 if val.flags["C_CONTIGUOUS"] and not val.flags["F_CONTIGUOUS"] else 0
-                N.call("snpmi_grm_add_dense_" + sfx, N.ptr(val), val.shape[0], val.shape[1], order_c)
-        finally:
-            N.call("snpmi_grm_end", 0, None, N.ptr(K))
+                s.add_dense(val)
         if whole:
             return (K.T if order == "F" else K), trained_list[0]
         # merged lazily: the reference merges only when the trained standardizer is asked for
@@ -219,14 +215,14 @@ def _read_bed_into_hbm(reader, order, dtype, num_threads):
     one; None for other readers."""
     from pysnptools_amd import hbm
     from pysnptools_amd.snpreader._dist2snp import _Dist2Snp
-    from pysnptools_amd.snpreader.bed import Bed
 
     if isinstance(reader, _Dist2Snp):
         return reader._convert(order, dtype, False, num_threads, to_hbm=True)
     base, rows, cols = _resolve(reader)
-    if _is_snpgen(base):
+    source = G.source_kind(base, rows)
+    if source in (G.SNPGEN, G.SNPGEN_IIDS):
         return _snpgen_into_hbm(base, rows, cols, order, dtype)
-    if not isinstance(base, Bed):
+    if source != G.BED:
         return None
     base._run_once()
     if dtype not in (np.float32, np.float64, np.int8):
@@ -251,53 +247,38 @@ def _read_and_standardize(reader, standardizer, order="F", dtype=np.float64, for
     straight to standardized values through a per-SNP table (the same f64 formula, so the values and
     stats are bit-identical to the two calls), writing the values once instead of decoding them and
     then reading + rewriting them.  Other readers / standardizers, and ``force_python_only=True``
-    (the caller asked for the reference's separate read + standardize steps), take the two calls."""
+    (the caller asked for the reference's separate read + standardize steps), take the two calls.
+    An all-iid SnpGen runs as per-SNP stats from the code counts and a decode through the per-SNP
+    table (snpmi_dev_snp_stats + snpmi_dev_decode), the packed codes never leaving HBM."""
     from pysnptools_amd import hbm
-    from pysnptools_amd.snpreader.bed import Bed
     from pysnptools_amd.snpreader.snpdata import SnpData
-    from pysnptools_amd.standardizer.standardizer import _std_args
     from pysnptools_amd.util import array_module
 
-    dtype = np.dtype(dtype)
-    args = _std_args(standardizer) if dtype in (np.float32, np.float64) else None
-    base, rows, cols = _resolve(reader) if args is not None and args[0] != N.STD_NONE else (None, None, None)
-    if not force_python_only and rows is None and _is_snpgen(base):
-        return _snpgen_read_and_standardize(reader, base, cols, standardizer, args, order, dtype)
-    if force_python_only or not isinstance(base, Bed):
+    p = None if force_python_only else G.plan(reader, standardizer, dtype)
+    if p is None or p.kind == N.STD_NONE or p.source not in (G.BED, G.SNPGEN):
         return reader.read(order=order, dtype=dtype).standardize(standardizer, return_trained=True,
                                                                  force_python_only=force_python_only,
                                                                  num_threads=num_threads)
-    kind, a, b, use_stats, _, _ = args
-    base._run_once()
-    sid = reader.sid
     order = "F" if order == "A" else order
-    ri, ci = N.index_array(rows), N.index_array(cols)
-    n = base.iid_count if ri is None else len(ri)
-    m = base.sid_count if ci is None else len(ci)
-    stats = (np.ascontiguousarray(standardizer.stats_for(sid), dtype=dtype) if use_stats
-             else np.empty((m, 2), dtype=dtype))
+    stats = p.stats()
     xp = array_module(None)
-    out = (hbm.empty if xp is hbm else np.empty)((n, m), dtype=dtype, order=order)
-    threads = get_num_threads(num_threads if num_threads is not None else base._num_threads)
-    N.call("snpmi_bed_read_standardize_" + N.suffix(dtype), base.filename.encode(), base.iid_count, base.sid_count,
-           int(bool(base.count_A1)), N.ptr(ri), n, N.ptr(ci), m, 1 if order == "C" else 0, kind, a, b,
-           int(use_stats), N.ptr(stats), N.ptr(out), threads)
-    data = SnpData(reader.iid, sid, out, pos=reader.pos, name=str(reader), xp=xp)
+    if p.source == G.SNPGEN:
+        out = p.base._decode(p.col_index(), order, p.dtype, std=(p.kind, p.a, p.b, p.use_stats), stats=stats,
+                             to_hbm=xp is hbm)
+    else:
+        base = p.base
+        base._run_once()
+        ri, ci = N.index_array(p.rows), N.index_array(p.cols)
+        out = (hbm.empty if xp is hbm else np.empty)((p.n, p.m), dtype=p.dtype, order=order)
+        N.call("snpmi_bed_read_standardize_" + p.sfx, base.filename.encode(), base.iid_count, base.sid_count,
+               int(bool(base.count_A1)), N.ptr(ri), p.n, N.ptr(ci), p.m, 1 if order == "C" else 0, *p.std,
+               N.ptr(stats), N.ptr(out), p.threads(num_threads))
+    data = SnpData(reader.iid, p.sid, out, pos=reader.pos, name=str(reader), xp=xp)
     data._std_string_list.append(str(standardizer))
-    return data, _trained_from(standardizer, kind, a, b, sid, stats)
+    return data, p.trained(stats)
 
 
 # ---------------------------------------------------------------------- SnpGen: generated in HBM
-def _is_snpgen(base):
-    from pysnptools_amd.snpreader.snpgen import SnpGen
-
-    return isinstance(base, SnpGen)
-
-
-def _snpgen_cols(base, cols):
-    return np.arange(base.sid_count) if cols is None else np.asarray(cols)
-
-
 def _snpgen_into_hbm(base, rows, cols, order, dtype):
     """``read(xp='hbm')`` of a SnpGen (or a subset of one): generated and decoded in HBM.  A float
     iid subset is gathered there too (the sub_matrix kernel); an int8 iid subset, which that kernel
@@ -308,60 +289,13 @@ def _snpgen_into_hbm(base, rows, cols, order, dtype):
     if dtype not in (np.float32, np.float64, np.int8):
         raise ValueError("dtype '{0}' not supported; use float32, float64 or int8".format(dtype))
     order = "F" if order == "A" else order
-    col_index = _snpgen_cols(base, cols)
+    col_index = np.arange(base.sid_count) if cols is None else np.asarray(cols)
     if rows is None:
         return base._decode(col_index, order, dtype, to_hbm=True)
     if dtype == np.int8 or len(rows) == 0 or len(col_index) == 0:
         return hbm.asarray(base._read(rows, cols, order, dtype, False, False, None), order=order)
     full = base._decode(col_index, order, dtype, to_hbm=True)
     return sub_matrix(full, rows, np.arange(len(col_index)), order=order, dtype=dtype)
-
-
-def _snpgen_read_and_standardize(reader, base, cols, standardizer, args, order, dtype):
-    """read + standardize of an all-iid SnpGen as per-SNP stats from the code counts and a decode
-    through the per-SNP table (snpmi_dev_snp_stats + snpmi_dev_decode), the packed codes never
-    leaving HBM."""
-    from pysnptools_amd import hbm
-    from pysnptools_amd.snpreader.snpdata import SnpData
-    from pysnptools_amd.util import array_module
-
-    kind, a, b, use_stats, _, _ = args
-    sid = reader.sid
-    order = "F" if order == "A" else order
-    stats = (np.ascontiguousarray(standardizer.stats_for(sid), dtype=dtype) if use_stats
-             else np.empty((len(sid), 2), dtype=dtype))
-    xp = array_module(None)
-    out = base._decode(_snpgen_cols(base, cols), order, dtype, std=(kind, a, b, use_stats), stats=stats,
-                       to_hbm=xp is hbm)
-    data = SnpData(reader.iid, sid, out, pos=reader.pos, name=str(reader), xp=xp)
-    data._std_string_list.append(str(standardizer))
-    return data, _trained_from(standardizer, kind, a, b, sid, stats)
-
-
-def _snpgen_grm(base, cols, n, kind, a, b, use_stats, stats, diag_k_to_n, fptr, K, dtype, chunk_bytes=1 << 30):
-    """K of an all-iid SnpGen: packed batches are generated in HBM and added to the GRM session
-    (snpmi_grm_begin / add_packed / end) chunk by chunk -- the values never exist as floats and K
-    is never built from host values.  Chunks are whole batches when the SNPs are a contiguous range;
-    otherwise a batch whose SNPs fall into two chunks is generated once for each.  Every batch seed
-    is range-checked before the session opens."""
-    sfx = N.suffix(dtype)
-    col_index = _snpgen_cols(base, cols)
-    base._check_seeds(col_index)
-    pitch = int(N.lib().snpmi_packed_pitch(n))
-    bs = int(base._block_size)
-    step = max(bs, chunk_bytes // pitch // bs * bs)
-    N.call("snpmi_grm_begin", n, N.dt_code(dtype))
-    try:
-        for c0 in range(0, len(col_index), step):
-            here = slice(c0, min(c0 + step, len(col_index)))
-            packed, _ = base._packed(col_index[here])
-            st = np.ascontiguousarray(stats[here])
-            N.call("snpmi_grm_add_packed_" + sfx, N.ptr(packed), pitch, n, here.stop - here.start, 0, kind, a, b,
-                   int(use_stats), N.ptr(st))
-            if not use_stats:
-                stats[here] = st
-    finally:
-        N.call("snpmi_grm_end", int(bool(diag_k_to_n)), fptr, N.ptr(K))
 
 
 def _resolve(reader):
@@ -378,156 +312,59 @@ def _resolve(reader):
     return reader, None, None
 
 
-def _trained_from(standardizer, kind, a, b, sid, stats):
-    from pysnptools_amd import standardizer as stdizer
-
-    if kind == N.STD_NONE:
-        return stdizer.Identity()
-    if isinstance(standardizer, (stdizer.UnitTrained, stdizer.BetaTrained)):
-        return standardizer
-    if kind == N.STD_UNIT:
-        return stdizer.UnitTrained(sid, stats)
-    return stdizer.BetaTrained(standardizer.a, standardizer.b, sid, stats)
-
-
-def _bed_pieces(base):
-    """The _MergeSIDs behind a DistributedBed / _MergeSIDs whose pieces are all Beds, else None."""
-    from pysnptools_amd.snpreader._mergesids import _MergeSIDs
-    from pysnptools_amd.snpreader.bed import Bed
-    from pysnptools_amd.snpreader.distributedbed import DistributedBed
-
-    if isinstance(base, DistributedBed):
-        base._run_once()
-        base = base._merge
-    if isinstance(base, _MergeSIDs) and all(isinstance(r, Bed) for r in base.reader_list):
-        base._run_once()
-        return base
-    return None
-
-
-def _add_pieces(merged, rows, cols, n, kind, a, b, use_stats, stats, dtype, num_threads, only=None):
-    """snpmi_grm_add_bed_* for every piece holding requested SNPs (``only``: piece subset)."""
-    sfx = N.suffix(dtype)
-    col_index = np.arange(merged.col_count) if cols is None else np.asarray(cols)
-    ri = N.index_array(rows)
-    for k, here, rel in merged._pieces(col_index):
-        if only is not None and k not in only:
-            continue
-        piece = merged.reader_list[k]
-        pst = np.ascontiguousarray(stats[here])
-        N.call("snpmi_grm_add_bed_" + sfx, piece.filename.encode(), merged.row_count,
-               int(merged.col_count_list[k]), int(bool(piece.count_A1)), N.ptr(ri), n, N.ptr(N.index_array(rel)),
-               len(rel), kind, a, b, int(use_stats), N.ptr(pst), get_num_threads(num_threads))
-        if not use_stats:
-            stats[here] = pst
-
-
-def _grm_pieces(merged, rows, cols, n, kind, a, b, use_stats, stats, diag_k_to_n, fptr, K, dtype, num_threads):
-    """One GPU session over the pieces: K accumulates in HBM across files (snpmi_grm_begin/add/end)."""
-    N.call("snpmi_grm_begin", n, N.dt_code(dtype))
-    try:
-        _add_pieces(merged, rows, cols, n, kind, a, b, use_stats, stats, dtype, num_threads)
-    finally:
-        N.call("snpmi_grm_end", int(bool(diag_k_to_n)), fptr, N.ptr(K))
-
-
-def _dist_grm(val, col0, cols, max_weight, n, kind, a, b, use_stats, stats, diag_k_to_n, fptr, K, dtype, block_size):
-    """K of ``dist.as_snp()`` over SNPs [col0, col0 + cols) of the stored distributions ``val``: one
-    GRM session, each block of ``block_size`` SNPs converted to expected values straight into the
-    SYRK's operand buffer, standardized there and accumulated (snpmi_grm_add_dist_*) -- the values
-    never exist on the host.  Whole / blocked as the reference's loop (snpreader.py:629)."""
-    sfx = N.suffix(dtype)
-    whole = block_size is None or cols <= block_size or cols <= n
-    step = max(cols if whole else int(block_size), 1)
-    order_c = 1 if (val.flags["C_CONTIGUOUS"] and not val.flags["F_CONTIGUOUS"]) else 0
-    N.call("snpmi_grm_begin", n, N.dt_code(dtype))
-    try:
-        for c0 in range(0, cols, step):
-            here = slice(c0, min(c0 + step, cols))
-            st = np.ascontiguousarray(stats[here])
-            N.call("snpmi_grm_add_dist_" + sfx, N.ptr(val), n, int(val.shape[1]), col0 + c0, here.stop - here.start,
-                   order_c, float(max_weight), kind, a, b, int(use_stats), N.ptr(st))
-            if not use_stats:
-                stats[here] = st
-    finally:
-        N.call("snpmi_grm_end", int(bool(diag_k_to_n)), fptr, N.ptr(K))
-
-
 def _native_grm(reader, standardizer, dtype, num_threads, diag_k_to_n, block_size=None):
-    """Fused GPU GRM for Bed / SnpData / stored-distribution sources; None when not applicable."""
-    from pysnptools_amd.snpreader.bed import Bed
-    from pysnptools_amd.standardizer.standardizer import _std_args
-
-    if dtype not in (np.float32, np.float64):
-        return None
-    args = _std_args(standardizer)
-    if args is None:
-        return None
-    kind, a, b, use_stats, given, _ = args
-    base, rows, cols = _resolve(reader)
-    sid = reader.sid
-    if use_stats:
-        stats = np.ascontiguousarray(standardizer.stats_for(sid), dtype=dtype)
-    else:
-        stats = np.empty((len(sid), 2), dtype=dtype)
-    n = reader.iid_count
+    """Fused GPU GRM of the sources the plan (``_grm.plan``) knows -- (K, trained standardizer,
+    DiagKtoN factor or NaN) -- or None: the generic block loop applies.  A Bed and a SnpData are one
+    native call; pieces, an all-iid SnpGen and stored distributions are fed to one GRM session."""
+    from pysnptools_amd import dist as dist_mod
     from pysnptools_amd import hbm
     from pysnptools_amd.util import _on_device
 
-    from pysnptools_amd.snpreader._dist2snp import _Dist2Snp, _stored_range
-
-    dist_src = None
-    if isinstance(base, _Dist2Snp):  # dist.as_snp(): only over stored distributions, else the block loop
-        dist_src = _stored_range(base.distreader, dtype)
-        if dist_src is None:
-            return None
-    # K stays in HBM when the source values do or ARRAY_MODULE=hbm (snpreader.py:638-643)
-    src_val = dist_src[0] if dist_src is not None else getattr(base, "val", None)
-    K = (hbm.empty if _on_device(src_val) else np.empty)((n, n), dtype=dtype)
-    factor = np.full(1, np.nan, dtype=np.float64)
-    fptr = factor.ctypes.data_as(N.ctypes.POINTER(N.ctypes.c_double))
-    sfx = N.suffix(dtype)
-    merged = _bed_pieces(base)
-    from pysnptools_amd import dist as dist_mod
-
+    p = G.plan(reader, standardizer, dtype)
+    if p is None or p.source in (G.NONE, G.SNPGEN_IIDS) or (p.source == G.DIST and p.src is None):
+        return None
     group = dist_mod.current()
-    if group is not None and group.world > 1 and (merged is not None or isinstance(base, Bed)):
+    multi = group is not None and group.world > 1
+    if multi and p.source in (G.SNPGEN, G.DIST):
+        return None  # multi-rank groups take the generic block loop
+    # K stays in HBM when the source values do or ARRAY_MODULE=hbm (snpreader.py:638-643)
+    src_val = p.src[0] if p.source == G.DIST else getattr(p.base, "val", None)
+    K = (hbm.empty if _on_device(src_val) else np.empty)((p.n, p.n), dtype=dtype)
+    if multi and p.source in (G.BED, G.PIECES):
         # one process per GPU (pysnptools_amd.dist.init_from_env): every rank calls read_kernel,
         # streams its SNP shard / pieces, and the RCCL all-reduce gives every rank the same K
         from pysnptools_amd import shard
 
-        run = shard.grm_pieces if merged is not None else shard.grm_sharded
+        run = shard.grm_pieces if p.source == G.PIECES else shard.grm_sharded
         return run(reader, standardizer, dtype=dtype, collective="allreduce", diag_k_to_n=diag_k_to_n, out=K,
                    num_threads=num_threads, dist=group)
-    if merged is not None:
-        _grm_pieces(merged, rows, cols, n, kind, a, b, use_stats, stats, diag_k_to_n, fptr, K, dtype, num_threads)
-    elif dist_src is not None:
-        if group is not None and group.world > 1:
-            return None  # multi-rank groups take the generic block loop
-        _dist_grm(dist_src[0], dist_src[1], dist_src[2], base.max_weight, n, kind, a, b, use_stats, stats,
-                  diag_k_to_n, fptr, K, dtype, block_size)
-    elif _is_snpgen(base):
-        if rows is not None or (group is not None and group.world > 1):
-            return None  # iid subsets and multi-rank groups take the generic block loop
-        _snpgen_grm(base, cols, n, kind, a, b, use_stats, stats, diag_k_to_n, fptr, K, dtype)
-    elif isinstance(base, Bed):
+    stats = p.stats()
+    factor = np.full(1, np.nan, dtype=np.float64)
+    tail = (int(bool(diag_k_to_n)), factor.ctypes.data_as(N.ctypes.POINTER(N.ctypes.c_double)), N.ptr(K))
+    if p.source == G.BED:
+        base = p.base
         base._run_once()
-        ri, ci = N.index_array(rows), N.index_array(cols)
-        N.call("snpmi_grm_bed_" + sfx, base.filename.encode(), base.iid_count, base.sid_count, int(bool(base.count_A1)),
-               N.ptr(ri), n, N.ptr(ci), len(sid), kind, a, b, int(use_stats), N.ptr(stats), int(bool(diag_k_to_n)),
-               fptr, N.ptr(K), get_num_threads(num_threads))
-    elif hasattr(base, "val") and base.val.ndim == 2:
-        if rows is None and cols is None:
-            val = base.val
-        else:
-            val = base._read(rows, cols, "A", base.val.dtype, False, True, num_threads)
+        ri, ci = N.index_array(p.rows), N.index_array(p.cols)
+        N.call("snpmi_grm_bed_" + p.sfx, base.filename.encode(), base.iid_count, base.sid_count,
+               int(bool(base.count_A1)), N.ptr(ri), p.n, N.ptr(ci), p.m, *p.std, N.ptr(stats), *tail,
+               get_num_threads(num_threads))
+    elif p.source == G.DENSE:
+        val = p.base.val
+        if p.rows is not None or p.cols is not None:
+            val = p.base._read(p.rows, p.cols, "A", val.dtype, False, True, num_threads)
         val = val if val.dtype == dtype else val.astype(dtype, order="K")
         if not (val.flags["C_CONTIGUOUS"] or val.flags["F_CONTIGUOUS"]):
             val = np.ascontiguousarray(val)
-        order_c = 1 if val.flags["C_CONTIGUOUS"] else 0
-        N.call("snpmi_grm_dense_" + sfx, N.ptr(val), val.shape[0], val.shape[1], order_c, kind, a, b, int(use_stats),
-               N.ptr(stats), int(bool(diag_k_to_n)), fptr, N.ptr(K))
+        N.call("snpmi_grm_dense_" + p.sfx, N.ptr(val), val.shape[0], val.shape[1], G.order_c(val), *p.std,
+               N.ptr(stats), *tail)
     else:
-        return None
-    trained = _trained_from(standardizer, kind, a, b, sid, stats)
-    return K, trained, float(factor[0])
+        if p.source == G.SNPGEN:
+            p.base._check_seeds(p.col_index())  # every batch seed, before the session opens
+        with G.session(p.n, dtype, K, diag_k_to_n, factor) as s:
+            if p.source == G.PIECES:
+                G.feed_pieces(s, p, stats, num_threads)
+            elif p.source == G.SNPGEN:
+                _snpgen_grm(s, p, stats)
+            else:
+                G.feed_dist(s, p, stats, block_size)
+    return K, p.trained(stats), float(factor[0])

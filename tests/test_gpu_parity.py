@@ -302,6 +302,20 @@ def test_grm_dense_snpdata_vs_reference():
             assert np.array_equal(d.val, np.array(xr, dtype=dtype), equal_nan=True)  # input untouched
 
 
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("order", ["C", "F"])
+@pytest.mark.parametrize("shape", [(6, 1), (1, 6)])
+def test_grm_dense_one_row_or_column(shape, order, dtype):
+    """An array of one row or one column is both C- and F-contiguous: the same memory under either
+    order flag.  Small-integer products are exact on both GRM paths."""
+    val = np.array(np.arange(6).reshape(shape) % 3, dtype=dtype, order=order)
+    assert val.flags["C_CONTIGUOUS"] and val.flags["F_CONTIGUOUS"]
+    d = SnpData(iid=[["a", str(i)] for i in range(shape[0])], sid=[str(j) for j in range(shape[1])], val=val)
+    k = d.read_kernel(Identity(), dtype=dtype).val
+    want = val.astype(np.float64) @ val.astype(np.float64).T
+    assert k.dtype == dtype and np.array_equal(k, want)
+
+
 def test_merge_std_block_size_invariance():
     """kernelreader/test.py:44-54: block_size=1 == block_size=None."""
     np.random.seed(0)
