@@ -355,6 +355,19 @@ int snpmi_dev_snpgen_rounds(uint64_t* batch_rounds);
 /* the raw stream, for pinning it to numpy: count doubles of RandomState(seed32).random_sample into
  * device memory (one workgroup; synchronous) */
 int snpmi_dev_mt19937_random_sample(uint32_t seed32, uint64_t count, double* out_dev);
+/* DistGen (distreader/distgen.py:110-165): the requested SNPs' genotype distributions, all iids,
+ * bit for bit the reference's values (a float32 output is the float64 value rounded once).  out:
+ * device, tight n_iid x n_sel x 3 in C order (out_order_c) or NumPy's F order of the 3-D array
+ * (strides 1, n_iid, n_iid * n_sel elements); column k = SNP sid_idx[k].  sid_idx (any order,
+ * repeats allowed) is a host array.  SNP s is column s % block_size of batch s / block_size, one
+ * MT19937 stream seeded with seed + batch * block_size, always of block_size SNPs; a batch seed
+ * above 2^32 - 1 is SNPMI_E_ARG, checked for every batch before any launch.  Every batch touched is
+ * generated once per call, by one workgroup, with no device scratch beyond the column tables.
+ * n_iid == 0 or n_sel == 0 launches nothing.  Synchronous. */
+int snpmi_dev_distgen_f32(float* out, uint64_t n_iid, uint64_t seed, uint64_t block_size, const uint64_t* sid_idx,
+                          uint64_t n_sel, int out_order_c);
+int snpmi_dev_distgen_f64(double* out, uint64_t n_iid, uint64_t seed, uint64_t block_size, const uint64_t* sid_idx,
+                          uint64_t n_sel, int out_order_c);
 /* selected .bed columns (all iids) into a host buffer at `pitch` bytes per column (zero pad) --
  * the gather half of the file readers (bed.py:337-343), for the cfg5 plan's per-rank shares */
 int snpmi_bed_gather_packed(const char* path, uint64_t n_iid, uint64_t n_sid, const uint64_t* sid_idx, uint64_t n_sel,

@@ -15,8 +15,10 @@ from pysnptools_amd import _native as N
 from pysnptools_amd.util import get_num_threads
 
 # source kinds
-BED, PIECES, SNPGEN, SNPGEN_IIDS, DIST, DENSE, NONE = "bed", "pieces", "snpgen", "snpgen_iids", "dist", "dense", None
+BED, PIECES, SNPGEN, SNPGEN_IIDS, DIST, DISTGEN, DENSE, NONE = ("bed", "pieces", "snpgen", "snpgen_iids", "dist",
+                                                                "distgen", "dense", None)
 SNPGEN_CHUNK_BYTES = 1 << 30  # packed SNPs generated in HBM per add_packed
+DISTGEN_CHUNK_BYTES = 1 << 30  # distributions generated in HBM per add_dist
 
 
 def order_c(val):
@@ -32,7 +34,9 @@ def require_float(dtype):
 
 def source_kind(base, rows=None):
     """The one ladder over reader types: which kind of GRM source the innermost reader ``base``
-    (``_resolve``), read at iids ``rows``, is.  DIST is any ``dist.as_snp()``: see ``Plan.src``."""
+    (``_resolve``), read at iids ``rows``, is.  DISTGEN is ``as_snp()`` of a DistGen read at every
+    iid, DIST any other ``dist.as_snp()``: see ``Plan.src``."""
+    from pysnptools_amd.distreader.distgen import generated_range
     from pysnptools_amd.snpreader._dist2snp import _Dist2Snp
     from pysnptools_amd.snpreader.bed import Bed
     from pysnptools_amd.snpreader.snpgen import SnpGen
@@ -40,7 +44,8 @@ def source_kind(base, rows=None):
     if _bed_pieces(base) is not None:
         return PIECES
     if isinstance(base, _Dist2Snp):
-        return DIST
+        # (an iid subset of a DistGen is a DIST without stored values: the generic block loop)
+        return DISTGEN if generated_range(base.distreader) is not None else DIST
     if isinstance(base, SnpGen):
         return SNPGEN if rows is None else SNPGEN_IIDS  # iid subsets take the generic block loop
     if isinstance(base, Bed):
@@ -80,7 +85,8 @@ class Plan(object):
     (``_resolve``), ``kind, a, b, use_stats`` (``std``: as the ABI takes them; ``args``: all of
     ``_std_args``), ``sid, n, m``, the dtype and its suffix, ``source`` (a source kind above) and
     ``src``: the _MergeSIDs of PIECES; the (array, col0, cols) of DIST (``_stored_range``), None when
-    the distributions are not stored ones -- then no fused route applies."""
+    the distributions are not stored ones -- then no fused route applies; the (DistGen, SNP index
+    array) of DISTGEN (``generated_range``)."""
 
     def __init__(self, reader, standardizer, dtype, args):
         from pysnptools_amd.snpreader.snpreader import _resolve
@@ -97,10 +103,12 @@ class Plan(object):
     def src(self):
         """Looked up on first use: ``_stored_range`` may load a file."""
         if "_src" not in self.__dict__:
+            from pysnptools_amd.distreader.distgen import generated_range
             from pysnptools_amd.snpreader._dist2snp import _stored_range
 
             self._src = (_bed_pieces(self.base) if self.source == PIECES else
-                         _stored_range(self.base.distreader, self.dtype) if self.source == DIST else None)
+                         _stored_range(self.base.distreader, self.dtype) if self.source == DIST else
+                         generated_range(self.base.distreader) if self.source == DISTGEN else None)
         return self._src
 
     def stats(self, zeros=False):
@@ -242,3 +250,24 @@ def feed_dist(s, p, stats, block_size):
         here = slice(c0, min(c0 + step, cols))
         _add_with_stats(p, stats, here, lambda st: s.add_dist(val, col0 + c0, here.stop - here.start,
                                                               p.base.max_weight, p.std, st))
+
+
+def feed_distgen(s, p, stats, chunk_bytes=DISTGEN_CHUNK_BYTES):
+    """``as_snp()`` of an all-iid DistGen: the distributions are generated chunk by chunk into one
+    reused HBM buffer (C order, the stream's own) and each chunk is converted straight into the
+    SYRK's operand buffer -- the triples never exist on the host.  Chunks are whole batches when the
+    SNPs are a contiguous range; otherwise a batch whose SNPs fall into two chunks is generated
+    once for each."""
+    from pysnptools_amd import hbm
+
+    gen, cols = p.src
+    bs = int(gen._block_size)
+    step = max(bs, chunk_bytes // (3 * max(p.n, 1) * p.dtype.itemsize) // bs * bs)
+    buf = hbm.empty((p.n, min(step, max(len(cols), 1)), 3), dtype=p.dtype, order="C")
+    for c0 in range(0, len(cols), step):
+        here = slice(c0, min(c0 + step, len(cols)))
+        count = here.stop - here.start
+        # the chunk's n x count x 3 triples, tight, at the start of the buffer
+        val = buf if count == buf.shape[1] else hbm.HbmArray((p.n, count, 3), p.dtype, "C", _base=buf, _ptr=buf.ptr)
+        gen._generate_into(val, cols[here])
+        _add_with_stats(p, stats, here, lambda st: s.add_dist(val, 0, count, p.base.max_weight, p.std, st))

@@ -116,6 +116,8 @@ _SIGS = {
     "snpmi_dev_snpgen_bed": [_vp, _u64, _u64, _u64, _u64, _vp, _u64, _vp, _vp, _i32, _u64],
     "snpmi_dev_snpgen_rounds": [_u64p],
     "snpmi_dev_mt19937_random_sample": [ctypes.c_uint32, _u64, _vp],
+    "snpmi_dev_distgen_f32": [_vp, _u64, _u64, _u64, _vp, _u64, _i32],
+    "snpmi_dev_distgen_f64": [_vp, _u64, _u64, _u64, _vp, _u64, _i32],
     "snpmi_bed_gather_packed": [_cp, _u64, _u64, _vp, _u64, _u64, _vp, _i32],
     "snpmi_dev_snp_stats": [_vp, _u64, _u64, _u64, _i32, _i32, _f64, _f64, _i32, _i32, _vp, _vp],
     "snpmi_dev_decode": [_vp, _u64, _u64, _u64, _vp, _i32, _i32, _vp, _u64],

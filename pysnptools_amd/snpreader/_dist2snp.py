@@ -4,7 +4,9 @@ The conversion ``(val * weights).sum(axis=-1)`` (_dist2snp.py:47-52) runs as ``s
 bit for bit NumPy's result.  Over stored or in-memory distributions (DistData, DistMemMap, DistNpz)
 with every iid and a contiguous ascending SNP range the kernel reads that range of the base array
 in place -- only those slabs of a host array are uploaded, nothing of an HBM-resident one moves;
-any other selection is gathered first (the 3-D ``sub_matrix`` path) and converted whole.
+any other selection is gathered first (the 3-D ``sub_matrix`` path) and converted whole.  Over a
+DistGen (every iid, any SNP selection) the distributions are generated in HBM (``snpmi_dev_distgen_*``)
+and converted there: the triples never visit the host.
 """
 import numpy as np
 
@@ -117,6 +119,7 @@ class _Dist2Snp(SnpReader):
 
     def _convert(self, order, dtype, force_python_only, num_threads, to_hbm):
         from pysnptools_amd import hbm
+        from pysnptools_amd.distreader.distgen import generated_range
         from pysnptools_amd.distreader.distreader import DistReader
         from pysnptools_amd.util import _on_device, asnumpy
 
@@ -131,6 +134,9 @@ class _Dist2Snp(SnpReader):
         if stored is not None:
             val, col0, cols = stored
             return dist_to_snp(val, col0, cols, self.max_weight, order, to_hbm=to_hbm)
+        generated = generated_range(self.distreader)
+        if generated is not None:
+            return self._convert_generated(generated, order, dtype, to_hbm)
         # all at once unless the SNPs outnumber both the block and the iids (_dist2snp.py:49-50)
         if self.block_size is None or self.sid_count <= self.block_size or self.sid_count <= self.iid_count:
             distdata = DistReader._as_distdata(self.distreader, dtype=dtype, order=order,
@@ -145,3 +151,30 @@ class _Dist2Snp(SnpReader):
             out[:, start:start + distdata.sid_count] = asnumpy(
                 dist_to_snp(distdata.val, 0, distdata.sid_count, self.max_weight, order))
         return hbm.asarray(out, order=order) if to_hbm else out
+
+    def _convert_generated(self, generated, order, dtype, to_hbm):
+        """Over a DistGen: the SNPs' triples are generated in HBM in C order (the stream's own) and
+        converted there, all at once or ``block_size`` SNPs at a time as the reference's loop
+        (_dist2snp.py:49-57), which bounds the triples held at once."""
+        from pysnptools_amd import hbm
+
+        gen, cols = generated
+        n, m = self.iid_count, len(cols)
+        order = "F" if order == "A" else order
+        if self.block_size is None or m <= self.block_size or m <= n:
+            out = dist_to_snp(gen._generate(cols, "C", dtype), 0, m, self.max_weight, order)
+            return out if to_hbm else out.get()
+        out = (hbm.empty if to_hbm else np.empty)((n, m), dtype=dtype, order=order)
+        size = dtype.itemsize
+        for start in range(0, m, self.block_size):
+            here = cols[start:start + self.block_size]
+            part = dist_to_snp(gen._generate(here, "C", dtype), 0, len(here), self.max_weight, order, to_hbm=True)
+            if not to_hbm:
+                out[:, start:start + len(here)] = part.get()
+            elif order == "F":  # whole columns: one contiguous run
+                N.call("snpmi_dev_memcpy_d2d", N.ctypes.c_void_p(out.ptr + start * n * size), N.ptr(part), part.nbytes)
+            else:
+                N.call("snpmi_dev_memcpy_2d", N.ctypes.c_void_p(out.ptr + start * size), m * size, N.ptr(part),
+                       len(here) * size, len(here) * size, n)
+            N.call("snpmi_stream_sync")  # the block's buffers are released on the next turn
+        return out

@@ -11,6 +11,8 @@
 * ``dist.as_snp()`` over stored distributions (DistData / DistMemMap / DistNpz, all iids, a SNP
   range) converts each block of ``block_size`` SNPs straight into the SYRK's operand buffer and
   standardizes it there, inside one GRM session (``snpmi_grm_begin / add_dist / end``);
+* ``DistGen(...).as_snp()`` (all iids, any SNP subset) generates the distributions chunk by chunk in
+  HBM (``snpmi_dev_distgen_*``) and adds each chunk to the same kind of session;
 * anything else (custom readers or standardizers) follows the reference's block loop,
   each block's Z Z^T still computed on the GPU.
 
@@ -315,7 +317,8 @@ def _resolve(reader):
 def _native_grm(reader, standardizer, dtype, num_threads, diag_k_to_n, block_size=None):
     """Fused GPU GRM of the sources the plan (``_grm.plan``) knows -- (K, trained standardizer,
     DiagKtoN factor or NaN) -- or None: the generic block loop applies.  A Bed and a SnpData are one
-    native call; pieces, an all-iid SnpGen and stored distributions are fed to one GRM session."""
+    native call; pieces, an all-iid SnpGen, stored distributions and an all-iid DistGen are fed to
+    one GRM session."""
     from pysnptools_amd import dist as dist_mod
     from pysnptools_amd import hbm
     from pysnptools_amd.util import _on_device
@@ -325,7 +328,7 @@ def _native_grm(reader, standardizer, dtype, num_threads, diag_k_to_n, block_siz
         return None
     group = dist_mod.current()
     multi = group is not None and group.world > 1
-    if multi and p.source in (G.SNPGEN, G.DIST):
+    if multi and p.source in (G.SNPGEN, G.DIST, G.DISTGEN):
         return None  # multi-rank groups take the generic block loop
     # K stays in HBM when the source values do or ARRAY_MODULE=hbm (snpreader.py:638-643)
     src_val = p.src[0] if p.source == G.DIST else getattr(p.base, "val", None)
@@ -360,11 +363,15 @@ def _native_grm(reader, standardizer, dtype, num_threads, diag_k_to_n, block_siz
     else:
         if p.source == G.SNPGEN:
             p.base._check_seeds(p.col_index())  # every batch seed, before the session opens
+        elif p.source == G.DISTGEN:
+            p.src[0]._check_seeds(p.src[1])
         with G.session(p.n, dtype, K, diag_k_to_n, factor) as s:
             if p.source == G.PIECES:
                 G.feed_pieces(s, p, stats, num_threads)
             elif p.source == G.SNPGEN:
                 _snpgen_grm(s, p, stats)
+            elif p.source == G.DISTGEN:
+                G.feed_distgen(s, p, stats)
             else:
                 G.feed_dist(s, p, stats, block_size)
     return K, p.trained(stats), float(factor[0])
