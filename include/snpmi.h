@@ -368,6 +368,37 @@ int snpmi_dev_distgen_f32(float* out, uint64_t n_iid, uint64_t seed, uint64_t bl
                           uint64_t n_sel, int out_order_c);
 int snpmi_dev_distgen_f64(double* out, uint64_t n_iid, uint64_t seed, uint64_t block_size, const uint64_t* sid_idx,
                           uint64_t n_sel, int out_order_c);
+/* BGEN (distreader/bgen.py; the reference reads through the cbgen library).  Host side, no device:
+ * one walk of the file's variant index per call, stepping over the genotype blocks.  Layout 2 with
+ * compression none or zlib only (layout 1, zstd: SNPMI_E_FORMAT, as is a file that ends early,
+ * naming the variant and offset).  snpmi_bgen_open fills info[11]: variants, samples, the header's
+ * flags, the first variant's offset, 1 if the file has a sample identifier block, the widest
+ * sample / id / rsid / chromosome / alleles string in bytes (a variant's K alleles are joined with
+ * commas), the file size.  snpmi_bgen_index fills arrays sized from those: rec[variant][5] = file
+ * offset of the stored genotype bytes, their count, the inflated length, the position, K; and the
+ * strings as fixed-width NUL-padded rows (NumPy 'S<width>'; an array whose width is 0 is not
+ * written, samples also when the file has no sample block). */
+int snpmi_bgen_open(const char* path, uint64_t* info);
+int snpmi_bgen_index(const char* path, uint64_t n_variants, uint64_t n_samples, uint64_t* rec, char* samples,
+                     uint64_t w_sample, char* ids, uint64_t w_id, char* rsids, uint64_t w_rsid, char* chroms,
+                     uint64_t w_chrom, char* alleles, uint64_t w_alleles);
+/* Inflated layout-2 genotype blocks (diploid, unphased, biallelic: the caller has checked every
+ * block's header and length 10 + N + ceil(2 B N / 8)) -> distributions.  blocks: device, 8-byte
+ * aligned, blocks_bytes long; col_table: host, [cols][3] = byte offset of output column s's block
+ * (a multiple of 8, with 16 readable bytes behind the block), its bit depth B (1 ... 32) and its
+ * sample count N; two columns may name one block.  Row r is sample iid_idx[r] (host or device
+ * array, every entry below every N) or, iid_idx NULL, sample r (rows <= every N).  With D = 2^B - 1
+ * and (a, b) the sample's two B-bit integers: p0 = a / D, p1 = b / D, p2 = (D - (a + b)) / D, each
+ * one f64 division (a float32 output is that value rounded once); three quiet NaNs where the
+ * sample's missing bit is set.  out: device, the SNPs [col0, col0 + cols) of a tight rows x
+ * cols_total x 3 array in the layouts above (dist.hip).  rows == 0 or cols == 0 launches nothing.
+ * Synchronous. */
+int snpmi_dev_bgen_decode_f32(const uint8_t* blocks, uint64_t blocks_bytes, const uint64_t* col_table, uint64_t cols,
+                              const uint64_t* iid_idx, uint64_t rows, float* out, uint64_t cols_total, uint64_t col0,
+                              int out_order_c);
+int snpmi_dev_bgen_decode_f64(const uint8_t* blocks, uint64_t blocks_bytes, const uint64_t* col_table, uint64_t cols,
+                              const uint64_t* iid_idx, uint64_t rows, double* out, uint64_t cols_total, uint64_t col0,
+                              int out_order_c);
 /* selected .bed columns (all iids) into a host buffer at `pitch` bytes per column (zero pad) --
  * the gather half of the file readers (bed.py:337-343), for the cfg5 plan's per-rank shares */
 int snpmi_bed_gather_packed(const char* path, uint64_t n_iid, uint64_t n_sid, const uint64_t* sid_idx, uint64_t n_sel,

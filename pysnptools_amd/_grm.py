@@ -15,10 +15,11 @@ from pysnptools_amd import _native as N
 from pysnptools_amd.util import get_num_threads
 
 # source kinds
-BED, PIECES, SNPGEN, SNPGEN_IIDS, DIST, DISTGEN, DENSE, NONE = ("bed", "pieces", "snpgen", "snpgen_iids", "dist",
-                                                                "distgen", "dense", None)
+BED, PIECES, SNPGEN, SNPGEN_IIDS, DIST, DISTGEN, BGEN, DENSE, NONE = ("bed", "pieces", "snpgen", "snpgen_iids", "dist",
+                                                                      "distgen", "bgen", "dense", None)
 SNPGEN_CHUNK_BYTES = 1 << 30  # packed SNPs generated in HBM per add_packed
 DISTGEN_CHUNK_BYTES = 1 << 30  # distributions generated in HBM per add_dist
+BGEN_CHUNK_BYTES = 1 << 30  # inflated BGEN blocks staged, and triples decoded from them in HBM, per launch
 
 
 def order_c(val):
@@ -34,8 +35,9 @@ def require_float(dtype):
 
 def source_kind(base, rows=None):
     """The one ladder over reader types: which kind of GRM source the innermost reader ``base``
-    (``_resolve``), read at iids ``rows``, is.  DISTGEN is ``as_snp()`` of a DistGen read at every
-    iid, DIST any other ``dist.as_snp()``: see ``Plan.src``."""
+    (``_resolve``), read at iids ``rows``, is.  DISTGEN / BGEN is ``as_snp()`` of a DistGen / Bgen read
+    at every iid, DIST any other ``dist.as_snp()``: see ``Plan.src``."""
+    from pysnptools_amd.distreader.bgen import bgen_range
     from pysnptools_amd.distreader.distgen import generated_range
     from pysnptools_amd.snpreader._dist2snp import _Dist2Snp
     from pysnptools_amd.snpreader.bed import Bed
@@ -44,7 +46,9 @@ def source_kind(base, rows=None):
     if _bed_pieces(base) is not None:
         return PIECES
     if isinstance(base, _Dist2Snp):
-        # (an iid subset of a DistGen is a DIST without stored values: the generic block loop)
+        # (an iid subset of a DistGen or Bgen is a DIST without stored values: the generic block loop)
+        if bgen_range(base.distreader) is not None:
+            return BGEN
         return DISTGEN if generated_range(base.distreader) is not None else DIST
     if isinstance(base, SnpGen):
         return SNPGEN if rows is None else SNPGEN_IIDS  # iid subsets take the generic block loop
@@ -86,7 +90,7 @@ class Plan(object):
     ``_std_args``), ``sid, n, m``, the dtype and its suffix, ``source`` (a source kind above) and
     ``src``: the _MergeSIDs of PIECES; the (array, col0, cols) of DIST (``_stored_range``), None when
     the distributions are not stored ones -- then no fused route applies; the (DistGen, SNP index
-    array) of DISTGEN (``generated_range``)."""
+    array) of DISTGEN (``generated_range``); the (Bgen, variant index array) of BGEN (``bgen_range``)."""
 
     def __init__(self, reader, standardizer, dtype, args):
         from pysnptools_amd.snpreader.snpreader import _resolve
@@ -103,12 +107,14 @@ class Plan(object):
     def src(self):
         """Looked up on first use: ``_stored_range`` may load a file."""
         if "_src" not in self.__dict__:
+            from pysnptools_amd.distreader.bgen import bgen_range
             from pysnptools_amd.distreader.distgen import generated_range
             from pysnptools_amd.snpreader._dist2snp import _stored_range
 
             self._src = (_bed_pieces(self.base) if self.source == PIECES else
                          _stored_range(self.base.distreader, self.dtype) if self.source == DIST else
-                         generated_range(self.base.distreader) if self.source == DISTGEN else None)
+                         generated_range(self.base.distreader) if self.source == DISTGEN else
+                         bgen_range(self.base.distreader) if self.source == BGEN else None)
         return self._src
 
     def stats(self, zeros=False):
@@ -270,4 +276,23 @@ def feed_distgen(s, p, stats, chunk_bytes=DISTGEN_CHUNK_BYTES):
         # the chunk's n x count x 3 triples, tight, at the start of the buffer
         val = buf if count == buf.shape[1] else hbm.HbmArray((p.n, count, 3), p.dtype, "C", _base=buf, _ptr=buf.ptr)
         gen._generate_into(val, cols[here])
+        _add_with_stats(p, stats, here, lambda st: s.add_dist(val, 0, count, p.base.max_weight, p.std, st))
+
+
+def feed_bgen(s, p, stats, chunk_bytes=None):
+    """``as_snp()`` of an all-iid Bgen: the variants' blocks are inflated, staged and decoded chunk by
+    chunk into one reused HBM triple buffer (F order: the decode's 16-byte store form) and each chunk
+    is converted straight into the SYRK's operand buffer -- the triples never exist on the host.  A
+    chunk is bounded by its staged blocks and by its triples (``BGEN_CHUNK_BYTES`` each)."""
+    from pysnptools_amd import hbm
+
+    bgen, cols = p.src
+    chunks = list(bgen._chunks(cols, p.n, p.dtype.itemsize, chunk_bytes or BGEN_CHUNK_BYTES))
+    widest = max([c.stop - c.start for c in chunks] + [1])
+    buf = hbm.empty((p.n, widest, 3), dtype=p.dtype, order="F")
+    for here in chunks:
+        count = here.stop - here.start
+        # the chunk's n x count x 3 triples, tight, at the start of the buffer
+        val = buf if count == widest else hbm.HbmArray((p.n, count, 3), p.dtype, "F", _base=buf, _ptr=buf.ptr)
+        bgen._decode_into(val, count, 0, cols[here])
         _add_with_stats(p, stats, here, lambda st: s.add_dist(val, 0, count, p.base.max_weight, p.std, st))

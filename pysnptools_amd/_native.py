@@ -118,6 +118,10 @@ _SIGS = {
     "snpmi_dev_mt19937_random_sample": [ctypes.c_uint32, _u64, _vp],
     "snpmi_dev_distgen_f32": [_vp, _u64, _u64, _u64, _vp, _u64, _i32],
     "snpmi_dev_distgen_f64": [_vp, _u64, _u64, _u64, _vp, _u64, _i32],
+    "snpmi_bgen_open": [_cp, _u64p],
+    "snpmi_bgen_index": [_cp, _u64, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64],
+    "snpmi_dev_bgen_decode_f32": [_vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _u64, _i32],
+    "snpmi_dev_bgen_decode_f64": [_vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _u64, _i32],
     "snpmi_bed_gather_packed": [_cp, _u64, _u64, _vp, _u64, _u64, _vp, _i32],
     "snpmi_dev_snp_stats": [_vp, _u64, _u64, _u64, _i32, _i32, _f64, _f64, _i32, _i32, _vp, _vp],
     "snpmi_dev_decode": [_vp, _u64, _u64, _u64, _vp, _i32, _i32, _vp, _u64],

@@ -6,7 +6,8 @@ with every iid and a contiguous ascending SNP range the kernel reads that range 
 in place -- only those slabs of a host array are uploaded, nothing of an HBM-resident one moves;
 any other selection is gathered first (the 3-D ``sub_matrix`` path) and converted whole.  Over a
 DistGen (every iid, any SNP selection) the distributions are generated in HBM (``snpmi_dev_distgen_*``)
-and converted there: the triples never visit the host.
+and converted there: the triples never visit the host.  Over a Bgen (every iid, any SNP selection)
+they are decoded into HBM (``snpmi_dev_bgen_decode_*``) and converted there in the same way.
 """
 import numpy as np
 
@@ -119,6 +120,7 @@ class _Dist2Snp(SnpReader):
 
     def _convert(self, order, dtype, force_python_only, num_threads, to_hbm):
         from pysnptools_amd import hbm
+        from pysnptools_amd.distreader.bgen import bgen_range
         from pysnptools_amd.distreader.distgen import generated_range
         from pysnptools_amd.distreader.distreader import DistReader
         from pysnptools_amd.util import _on_device, asnumpy
@@ -137,6 +139,9 @@ class _Dist2Snp(SnpReader):
         generated = generated_range(self.distreader)
         if generated is not None:
             return self._convert_generated(generated, order, dtype, to_hbm)
+        decoded = bgen_range(self.distreader)
+        if decoded is not None:  # F order: the decode's 16-byte store form
+            return self._convert_generated(decoded, order, dtype, to_hbm, made_order="F")
         # all at once unless the SNPs outnumber both the block and the iids (_dist2snp.py:49-50)
         if self.block_size is None or self.sid_count <= self.block_size or self.sid_count <= self.iid_count:
             distdata = DistReader._as_distdata(self.distreader, dtype=dtype, order=order,
@@ -152,23 +157,24 @@ class _Dist2Snp(SnpReader):
                 dist_to_snp(distdata.val, 0, distdata.sid_count, self.max_weight, order))
         return hbm.asarray(out, order=order) if to_hbm else out
 
-    def _convert_generated(self, generated, order, dtype, to_hbm):
-        """Over a DistGen: the SNPs' triples are generated in HBM in C order (the stream's own) and
-        converted there, all at once or ``block_size`` SNPs at a time as the reference's loop
-        (_dist2snp.py:49-57), which bounds the triples held at once."""
+    def _convert_generated(self, generated, order, dtype, to_hbm, made_order="C"):
+        """Over a DistGen or a Bgen: the SNPs' triples are made in HBM (``_generate``) in
+        ``made_order`` (C: the DistGen stream's own) and converted there, all at once or
+        ``block_size`` SNPs at a time as the reference's loop (_dist2snp.py:49-57), which bounds the
+        triples held at once."""
         from pysnptools_amd import hbm
 
         gen, cols = generated
         n, m = self.iid_count, len(cols)
         order = "F" if order == "A" else order
         if self.block_size is None or m <= self.block_size or m <= n:
-            out = dist_to_snp(gen._generate(cols, "C", dtype), 0, m, self.max_weight, order)
+            out = dist_to_snp(gen._generate(cols, made_order, dtype), 0, m, self.max_weight, order)
             return out if to_hbm else out.get()
         out = (hbm.empty if to_hbm else np.empty)((n, m), dtype=dtype, order=order)
         size = dtype.itemsize
         for start in range(0, m, self.block_size):
             here = cols[start:start + self.block_size]
-            part = dist_to_snp(gen._generate(here, "C", dtype), 0, len(here), self.max_weight, order, to_hbm=True)
+            part = dist_to_snp(gen._generate(here, made_order, dtype), 0, len(here), self.max_weight, order, to_hbm=True)
             if not to_hbm:
                 out[:, start:start + len(here)] = part.get()
             elif order == "F":  # whole columns: one contiguous run

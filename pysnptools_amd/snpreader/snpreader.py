@@ -317,8 +317,8 @@ def _resolve(reader):
 def _native_grm(reader, standardizer, dtype, num_threads, diag_k_to_n, block_size=None):
     """Fused GPU GRM of the sources the plan (``_grm.plan``) knows -- (K, trained standardizer,
     DiagKtoN factor or NaN) -- or None: the generic block loop applies.  A Bed and a SnpData are one
-    native call; pieces, an all-iid SnpGen, stored distributions and an all-iid DistGen are fed to
-    one GRM session."""
+    native call; pieces, an all-iid SnpGen, stored distributions and an all-iid DistGen or Bgen are
+    fed to one GRM session."""
     from pysnptools_amd import dist as dist_mod
     from pysnptools_amd import hbm
     from pysnptools_amd.util import _on_device
@@ -328,7 +328,7 @@ def _native_grm(reader, standardizer, dtype, num_threads, diag_k_to_n, block_siz
         return None
     group = dist_mod.current()
     multi = group is not None and group.world > 1
-    if multi and p.source in (G.SNPGEN, G.DIST, G.DISTGEN):
+    if multi and p.source in (G.SNPGEN, G.DIST, G.DISTGEN, G.BGEN):
         return None  # multi-rank groups take the generic block loop
     # K stays in HBM when the source values do or ARRAY_MODULE=hbm (snpreader.py:638-643)
     src_val = p.src[0] if p.source == G.DIST else getattr(p.base, "val", None)
@@ -365,6 +365,8 @@ def _native_grm(reader, standardizer, dtype, num_threads, diag_k_to_n, block_siz
             p.base._check_seeds(p.col_index())  # every batch seed, before the session opens
         elif p.source == G.DISTGEN:
             p.src[0]._check_seeds(p.src[1])
+        elif p.source == G.BGEN:
+            p.src[0]._check(p.src[1])  # every variant's allele count, before the session opens
         with G.session(p.n, dtype, K, diag_k_to_n, factor) as s:
             if p.source == G.PIECES:
                 G.feed_pieces(s, p, stats, num_threads)
@@ -372,6 +374,8 @@ def _native_grm(reader, standardizer, dtype, num_threads, diag_k_to_n, block_siz
                 _snpgen_grm(s, p, stats)
             elif p.source == G.DISTGEN:
                 G.feed_distgen(s, p, stats)
+            elif p.source == G.BGEN:
+                G.feed_bgen(s, p, stats)
             else:
                 G.feed_dist(s, p, stats, block_size)
     return K, p.trained(stats), float(factor[0])
