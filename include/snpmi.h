@@ -422,6 +422,41 @@ int snpmi_dev_encode(const void* val, int dtype, int order_c, uint64_t ld, uint6
 /* iid gather: dst column j = src column j restricted to iids idx[0..n_out) */
 int snpmi_dev_repack(const uint8_t* src, uint64_t src_pitch, uint64_t n_src_iid, const uint64_t* idx,
                      uint64_t n_out_iid, uint64_t n_sid, uint8_t* dst, uint64_t dst_pitch);
+/* Products of the standardized genotypes with tall matrices, straight from the packed codes:
+ * Z[i, s] = lut[4 s + code(i, s)] (the LUT of snpmi_dev_snp_stats) is never written anywhere.
+ *   snpmi_dev_packed_tdot:  G = Z^T V   (n_sid x k)
+ *   snpmi_dev_packed_dot:   Y = Z W, or Y += Z W with accumulate != 0   (n_iid x k)
+ * so K V = Z (Z^T V) takes two calls and no K.  The reference has no call site for these: its
+ * callers use NumPy on SnpData.val (snps.val.T.dot(y)).
+ * Layout: every pointer is a device pointer; lut is [n_sid][4] of dtype (f32 / f64); a tall matrix
+ * with k columns is F order, column c at base + c * ld elements, ld >= its row count (V, Y: n_iid;
+ * G, W: n_sid), so the G of one call is the W of the other.  Elements between the row count and ld
+ * are neither read nor written.  k is any count: wider matrices are served in column panels.
+ * Errors (SNPMI_E_ARG before any launch): an ld below the row count, pitch % 64 != 0, pitch <
+ * ceil(n_iid / 4), another dtype.  n_iid == 0, n_sid == 0 or k == 0 launch nothing, except that the
+ * dot with n_sid == 0 and accumulate == 0 writes zeros.
+ * The calls run on the calling thread's stream and keep no state; their partial sums live in the
+ * library's cached scratch (snpmi_release_cache).
+ * iids: genotypes of iids >= n_iid are not added, whatever the unused codes of a column's last byte,
+ * its pad bytes up to pitch and the LUT hold.
+ * NaN: the products are IEEE FMAs, so a NaN LUT entry (the missing code under no standardization)
+ * gives what NumPy gives: NaN in the tdot row of a SNP with a missing genotype and in every dot row
+ * of an iid that has one, whatever V or W hold there; finite values everywhere else.
+ * Determinism: no atomics, one fixed order per sum, the same bits on every run.
+ *   tdot: a SNP's row depends on that SNP's codes, its LUT and V alone, not on the other SNPs of the
+ *     call.  Per column a lane adds its 16 iids, a wave its 64 lanes, a workgroup its 4 waves (4096
+ *     iids, in dtype); the 4096-iid chunks are then added in chunk order in f64 and rounded once.
+ *   dot: the SNPs are cut into segments of 256 from the call's first SNP; a segment's sum p_j is one
+ *     chain in dtype from zero, and Y = (((Y or 0) + p_0) + p_1) + ... in dtype, in segment order.
+ *     The accumulate form starts that fold from the value Y holds, so calls over consecutive SNP
+ *     chunks, each but the last a multiple of 256 SNPs, perform add by add the fold of one call over
+ *     all of them: the same bits.  (Y is stored in dtype between calls, so the fold across segments
+ *     cannot be kept in f64; in f32 a term passes through at most 256 + n_sid / 256 roundings, below
+ *     the 16384 of the f32 GRM's chains up to 4.1 million SNPs.) */
+int snpmi_dev_packed_tdot(const uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_t n_sid, const void* lut,
+                          int dtype, const void* V, uint64_t ldv, uint64_t k, void* G, uint64_t ldg);
+int snpmi_dev_packed_dot(const uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_t n_sid, const void* lut,
+                         int dtype, const void* W, uint64_t ldw, uint64_t k, void* Y, uint64_t ldy, int accumulate);
 /* GRM tiles: K_tiles holds the upper-triangle 128x128 tiles of an n x n K
  * (snpmi_grm_tile_bytes); accumulate != 0 adds to it. */
 uint64_t snpmi_grm_tile_bytes(uint64_t n_iid, int dtype);

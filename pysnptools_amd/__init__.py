@@ -14,6 +14,15 @@ from pysnptools_amd import _native  # noqa: F401
 _F64_GRM = {"crt": 0, "mfma": 1}
 
 
+def __getattr__(name):
+    # SnpOperator (pysnptools_amd.linop), imported on first use: the readers it needs import this package
+    if name == "SnpOperator":
+        from pysnptools_amd.linop import SnpOperator
+
+        return SnpOperator
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
 def set_grm_f64(path):
     """How float64 GRMs (the reference's default dtype) are computed on this process's GPU:
 

@@ -128,6 +128,8 @@ _SIGS = {
     "snpmi_dev_decode_standardize": [_vp, _u64, _u64, _u64, _i32, _i32, _f64, _f64, _i32, _i32, _vp, _vp, _vp, _u64],
     "snpmi_dev_encode": [_vp, _i32, _i32, _u64, _u64, _u64, _i32, _vp, _u64, ctypes.POINTER(ctypes.c_uint64)],
     "snpmi_dev_repack": [_vp, _u64, _u64, _vp, _u64, _u64, _vp, _u64],
+    "snpmi_dev_packed_tdot": [_vp, _u64, _u64, _u64, _vp, _i32, _vp, _u64, _u64, _vp, _u64],
+    "snpmi_dev_packed_dot": [_vp, _u64, _u64, _u64, _vp, _i32, _vp, _u64, _u64, _vp, _u64, _i32],
     "snpmi_dev_syrk_packed": [_vp, _u64, _u64, _u64, _vp, _i32, _vp, _i32],
     "snpmi_grm_rect_bytes": [_u64, _u64, _i32],
     "snpmi_rect_diag_pairs": [_vp, _u64, _vp, _u64, _vp, _u64, _u64p],

@@ -96,7 +96,9 @@ struct Device {
                 S_RECT, S_RECT_A, S_RECT_B, S_RECT_IDX_A, S_RECT_IDX_B, S_RECT_PLAN_A, S_RECT_PLAN_B, S_RECT_WIN_A,
                 S_RECT_WIN_B, S_RECT_PAIRS,
                 // dist.hip: staged slabs of a host distribution array, converted block on its way out
-                S_DIST, S_DIST_OUT, S_NUM };
+                S_DIST, S_DIST_OUT,
+                // matvec.hip: the partial sums of one launch, before their ordered fold
+                S_MATVEC, S_NUM };
     void* buf[S_NUM] = {};
     // chunk pipeline events (slot = chunk parity), all on-device ordering, no host spin:
     hipEvent_t staged[2] = {};    // copy stream: H2D of pinned slot done (host may refill it)
