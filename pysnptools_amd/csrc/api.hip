@@ -293,6 +293,20 @@ static void check_index(const uint64_t* idx, uint64_t n, uint64_t bound, const c
                           std::to_string(bound) + ")");
 }
 
+// The .bed selection block from the ABI's loose arguments: the only place where "a NULL index list
+// selects everything" becomes a count.
+static BedSel bed_sel(const char* path, uint64_t n_iid, uint64_t n_sid, int count_a1, const uint64_t* iid_idx,
+                      uint64_t n_out_iid, const uint64_t* sid_idx, uint64_t n_out_sid, int num_threads) {
+    return {path, n_iid, n_sid, count_a1, iid_idx, sid_idx, num_threads,
+            iid_idx ? n_out_iid : n_iid, sid_idx ? n_out_sid : n_sid};
+}
+// open the selection's file and range-check its index lists
+static void open_sel(BedMap& m, const BedSel& s) {
+    open_bed(m, s.path, s.n_iid, s.n_sid);
+    check_index(s.iid_idx, s.n_out, s.n_iid, "iid");
+    check_index(s.sid_idx, s.m_out, s.n_sid, "sid");
+}
+
 static bool is_identity(const uint64_t* idx, uint64_t n, uint64_t bound) {
     if (!idx) return true;
     if (n != bound) return false;
@@ -335,16 +349,16 @@ struct IidPlan {
     RepackPlan plan;                // gather plan of k_repack_lds / k_repack_win
 };
 
-static IidPlan plan_iids(Device& d, const uint64_t* iid_idx, uint64_t n_iid, uint64_t n_out) {
+static IidPlan plan_iids(Device& d, const BedSel& s) {
     IidPlan p;
-    p.n_in = n_iid;
-    p.n_out = iid_idx ? n_out : n_iid;
-    p.pitch_in = packed_pitch(n_iid);
+    p.n_in = s.n_iid;
+    p.n_out = s.n_out;
+    p.pitch_in = packed_pitch(s.n_iid);
     p.pitch_out = packed_pitch(p.n_out);
-    p.repack = !is_identity(iid_idx, p.n_out, n_iid);
+    p.repack = !is_identity(s.iid_idx, p.n_out, s.n_iid);
     if (p.repack && p.n_out) {
         p.idx_dev = (uint64_t*)d.get(Device::S_IDX, p.n_out * 8);
-        SNPMI_HIP(hipMemcpyAsync(p.idx_dev, iid_idx, p.n_out * 8, hipMemcpyHostToDevice, d.stream));
+        SNPMI_HIP(hipMemcpyAsync(p.idx_dev, s.iid_idx, p.n_out * 8, hipMemcpyHostToDevice, d.stream));
         uint32_t* plan = (uint32_t*)d.get(Device::S_IDX32, repack_plan_entries(p.n_out) * 4);
         uint32_t* win = (uint32_t*)d.get(Device::S_WIN, repack_win_entries(p.n_out) * 4);
         p.plan = launch_repack_plan(p.idx_dev, p.n_out, p.n_in, plan, win, d.stream);
@@ -428,22 +442,18 @@ static uint64_t chunk_snps(uint64_t per_snp_bytes, uint64_t budget = 1ull << 30)
 }
 
 // ====================================================================== BED read (+ standardize)
+// out_optional: the caller's own output counts (n_out_iid, n_out_sid, whatever the index lists) hold a 0
 template <typename T>
-static void bed_read_impl(const char* path, uint64_t n_iid, uint64_t n_sid, int count_a1, const uint64_t* iid_idx,
-                          uint64_t n_out_iid, const uint64_t* sid_idx, uint64_t n_out_sid, int order_c, int std_kind,
-                          double a, double b, int use_stats, T* stats, T* out, int num_threads) {
+static void bed_read_impl(const BedSel& s, int order_c, const StdArgs& sa, T* stats, T* out, bool out_optional) {
     std::lock_guard<std::recursive_mutex> lk(g_call_mutex);
-    SNPMI_REQUIRE(out != nullptr || (n_out_iid == 0 || n_out_sid == 0), SNPMI_E_ARG, "out is NULL");
+    SNPMI_REQUIRE(out != nullptr || out_optional, SNPMI_E_ARG, "out is NULL");
     BedMap m;
-    open_bed(m, path, n_iid, n_sid);
-    const uint64_t n_out = iid_idx ? n_out_iid : n_iid;
-    const uint64_t m_out = sid_idx ? n_out_sid : n_sid;
-    check_index(iid_idx, n_out, n_iid, "iid");
-    check_index(sid_idx, m_out, n_sid, "sid");
+    open_sel(m, s);
+    const uint64_t n_out = s.n_out, m_out = s.m_out;
     if (m_out == 0) return;
     Device& d = device();
-    const int nthreads = resolve_threads(num_threads);
-    IidPlan p = plan_iids(d, iid_idx, n_iid, n_out);
+    const int nthreads = resolve_threads(s.num_threads);
+    IidPlan p = plan_iids(d, s);
     const int dt = DT<T>::v;
     const bool dev_out = is_device_ptr(d, out);
     // device output: decode straight into it when its columns (F) meet the 16-B vector-store
@@ -453,7 +463,7 @@ static void bed_read_impl(const char* path, uint64_t n_iid, uint64_t n_sid, int 
                                                 (n_out * sizeof(T)) % 16 == 0));
     const uint64_t ldF = round_up(std::max<uint64_t>(n_out, 1), 16);
     const uint64_t C = chunk_snps(p.pitch_in + p.pitch_out + ldF * sizeof(T));
-    const bool stats_out = std_kind != SNPMI_STD_NONE && !use_stats;
+    const bool stats_out = sa.kind != SNPMI_STD_NONE && !sa.use_stats;
     // Three-stage pipeline over SNP chunks, two slots each: host gather + H2D (copy stream) of
     // chunk c, stats + decode of chunk c (compute stream), D2H + host copy-out of chunk c-1 (copy
     // stream, after `produced`).  PCIe runs both directions at once and the kernels of chunk c
@@ -483,16 +493,15 @@ static void bed_read_impl(const char* path, uint64_t n_iid, uint64_t n_sid, int 
     // per-SNP stats stay on the device for the whole call and cross PCIe once each way (a per-chunk
     // D2H on the copy stream would wait for that chunk's kernels and stall the next upload)
     T* st_all = (T*)d.get(Device::S_STATS, m_out * 2 * sizeof(T));
-    if (std_kind != SNPMI_STD_NONE && use_stats)
+    if (sa.kind != SNPMI_STD_NONE && sa.use_stats)
         SNPMI_HIP(hipMemcpyAsync(st_all, stats, m_out * 2 * sizeof(T), hipMemcpyHostToDevice, d.stream));
     for (uint64_t c0 = 0, ci = 0; c0 < m_out; c0 += C, ci++) {
         const uint64_t cnt = std::min(C, m_out - c0);
         const int slot = (int)(ci & 1);
-        const uint8_t* packed = stage_chunk(d, m, sid_idx, c0, cnt, p, nthreads, slot);
+        const uint8_t* packed = stage_chunk(d, m, s.sid_idx, c0, cnt, p, nthreads, slot);
         T* lut = (T*)d.get(Device::S_LUT, cnt * 4 * sizeof(T));
         T* st_dev = st_all + 2 * c0;
-        launch_snp_stats(packed, p.pitch_out, n_out, cnt, count_a1, std_kind, a, b, use_stats, dt, st_dev, lut,
-                         d.stream);
+        launch_snp_stats(packed, p.pitch_out, n_out, cnt, s.count_a1, sa, dt, st_dev, lut, d.stream);
         Pending q;
         q.c0 = c0;
         q.cnt = cnt;
@@ -603,7 +612,7 @@ static void standardize_impl(T* val, uint64_t rows, uint64_t cols, int order_c, 
                                            d.stream));
     if (use_stats) SNPMI_HIP(hipMemcpyAsync(ds, stats, cols * 2 * sizeof(T), hipMemcpyHostToDevice, d.stream));
     launch_dense_standardize(dv, rows, cols, order_c ? cols : rows, order_c, DT<T>::v,
-                             is_beta ? SNPMI_STD_BETA : SNPMI_STD_UNIT, a, b, use_stats, ds, d.stream);
+                             {is_beta ? SNPMI_STD_BETA : SNPMI_STD_UNIT, a, b, use_stats}, ds, d.stream);
     if (apply_in_place && !dev) d2h_bytes(d, val, dv, bytes, nthreads);
     if (!use_stats) SNPMI_HIP(hipMemcpyAsync(stats, ds, cols * 2 * sizeof(T), hipMemcpyDeviceToHost, d.stream));
     SNPMI_HIP(hipStreamSynchronize(d.stream));
@@ -902,19 +911,15 @@ static void grm_finish(Device& d, const T* tiles, uint64_t n, int diag_k_to_n, d
 // Stream the SNP columns of one .bed through stats and `syrk(packed, pitch, n, cnt, lut,
 // accumulate)` (first = overwrite).  Returns true if anything was written.
 template <typename T, class Syrk>
-static bool grm_stream_bed(Device& d, bool first, const char* path, uint64_t n_iid, uint64_t n_sid, int count_a1,
-                           const uint64_t* iid_idx, uint64_t n_out_iid, const uint64_t* sid_idx, uint64_t n_out_sid,
-                           int std_kind, double a, double b, int use_stats, T* stats, int num_threads, Syrk&& syrk) {
+static bool grm_stream_bed(Device& d, bool first, const BedSel& s, const StdArgs& sa, T* stats, Syrk&& syrk) {
     BedMap m;
-    open_bed(m, path, n_iid, n_sid);
-    const uint64_t n_out = iid_idx ? n_out_iid : n_iid;
-    const uint64_t m_out = sid_idx ? n_out_sid : n_sid;
-    check_index(iid_idx, n_out, n_iid, "iid");
-    check_index(sid_idx, m_out, n_sid, "sid");
+    open_sel(m, s);
+    const uint64_t n_out = s.n_out, m_out = s.m_out;
+    const int std_kind = sa.kind, use_stats = sa.use_stats;
     SNPMI_REQUIRE(stats != nullptr || std_kind == SNPMI_STD_NONE || m_out == 0, SNPMI_E_ARG, "stats is NULL");
-    const int nthreads = resolve_threads(num_threads);
+    const int nthreads = resolve_threads(s.num_threads);
     const int dt = DT<T>::v;
-    IidPlan p = plan_iids(d, iid_idx, n_iid, n_out);
+    IidPlan p = plan_iids(d, s);
     // ~0.5 GiB of packed codes per chunk keeps >= 2 chunks in flight for cfg4-sized inputs
     const uint64_t C = chunk_snps(p.pitch_in + p.pitch_out, 1ull << 29);
     const bool has_stats = std_kind != SNPMI_STD_NONE && m_out > 0 && n_out > 0;
@@ -939,11 +944,10 @@ static bool grm_stream_bed(Device& d, bool first, const char* path, uint64_t n_i
     }
     for (uint64_t c0 = 0, ci = 0; c0 < m_out && n_out > 0; ci++) {
         const uint64_t cnt = std::min(ci == 0 ? C1 : C, m_out - c0);
-        const uint8_t* packed = stage_chunk(d, m, sid_idx, c0, cnt, p, nthreads, (int)(ci & 1));
+        const uint8_t* packed = stage_chunk(d, m, s.sid_idx, c0, cnt, p, nthreads, (int)(ci & 1));
         T* lut = (T*)d.get(Device::S_LUT, std::min(C, m_out) * 4 * sizeof(T));
         T* st_dev = st_all + 2 * c0;
-        launch_snp_stats(packed, p.pitch_out, n_out, cnt, count_a1, std_kind, a, b, use_stats, dt, st_dev, lut,
-                         d.stream);
+        launch_snp_stats(packed, p.pitch_out, n_out, cnt, s.count_a1, sa, dt, st_dev, lut, d.stream);
         syrk(packed, p.pitch_out, n_out, cnt, (const T*)lut, !(first && !wrote));
         wrote = true;
         chunk_done(d, (int)(ci & 1));
@@ -962,32 +966,22 @@ static bool grm_stream_bed(Device& d, bool first, const char* path, uint64_t n_i
 
 // Accumulate the SNP columns of one .bed into the replicated upper-triangle tiles.
 template <typename T>
-static bool grm_add_bed(Device& d, T* tiles, bool first, const char* path, uint64_t n_iid, uint64_t n_sid,
-                        int count_a1, const uint64_t* iid_idx, uint64_t n_out_iid, const uint64_t* sid_idx,
-                        uint64_t n_out_sid, int std_kind, double a, double b, int use_stats, T* stats,
-                        int num_threads) {
-    return grm_stream_bed<T>(d, first, path, n_iid, n_sid, count_a1, iid_idx, n_out_iid, sid_idx, n_out_sid, std_kind,
-                             a, b, use_stats, stats, num_threads,
+static bool grm_add_bed(Device& d, T* tiles, bool first, const BedSel& s, const StdArgs& sa, T* stats) {
+    return grm_stream_bed<T>(d, first, s, sa, stats,
                              [&](const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t cnt, const T* lut, bool acc) {
                                  syrk_packed_auto(d, packed, pitch, n, cnt, lut, DT<T>::v, whole_dest(tiles, n), acc);
                              });
 }
 
 template <typename T>
-static void grm_bed_impl(const char* path, uint64_t n_iid, uint64_t n_sid, int count_a1, const uint64_t* iid_idx,
-                         uint64_t n_out_iid, const uint64_t* sid_idx, uint64_t n_out_sid, int std_kind, double a,
-                         double b, int use_stats, T* stats, int diag_k_to_n, double* factor, T* K_out,
-                         int num_threads) {
+static void grm_bed_impl(const BedSel& s, const StdArgs& sa, T* stats, int diag_k_to_n, double* factor, T* K_out) {
     std::lock_guard<std::recursive_mutex> lk(g_call_mutex);
-    const uint64_t n_out = iid_idx ? n_out_iid : n_iid;
-    SNPMI_REQUIRE(K_out != nullptr || n_out == 0, SNPMI_E_ARG, "K_out is NULL");
+    SNPMI_REQUIRE(K_out != nullptr || s.n_out == 0, SNPMI_E_ARG, "K_out is NULL");
     Device& d = device();
-    const uint64_t tile_bytes = n_tiles_upper(n_out) * kTile * kTile * sizeof(T);
+    const uint64_t tile_bytes = n_tiles_upper(s.n_out) * kTile * kTile * sizeof(T);
     T* tiles = (T*)d.get(Device::S_TILES, tile_bytes);
-    if (!grm_add_bed<T>(d, tiles, true, path, n_iid, n_sid, count_a1, iid_idx, n_out_iid, sid_idx, n_out_sid,
-                        std_kind, a, b, use_stats, stats, num_threads))
-        SNPMI_HIP(hipMemsetAsync(tiles, 0, tile_bytes, d.stream));
-    grm_finish(d, tiles, n_out, diag_k_to_n, factor, K_out);
+    if (!grm_add_bed<T>(d, tiles, true, s, sa, stats)) SNPMI_HIP(hipMemsetAsync(tiles, 0, tile_bytes, d.stream));
+    grm_finish(d, tiles, s.n_out, diag_k_to_n, factor, K_out);
 }
 
 // ---------------------------------------------------------------------- GRM session (several .bed files)
@@ -1001,6 +995,37 @@ static GrmSession g_session;
 
 static void* session_tiles(Device& d) {
     return d.get(Device::S_SESSION, n_tiles_upper(g_session.n) * kTile * kTile * dtype_size(g_session.dtype));
+}
+
+// What an add asks of the open session, in the order every entry point reports it: that there is
+// one, that it has the add's dtype, that it has the add's iid count.  The reduce forms check their
+// collective arguments between the dtype and the iid count (check_reduce_args), hence the pieces.
+static void session_check_open() {
+    SNPMI_REQUIRE(g_session.active, SNPMI_E_ARG, "no GRM session (call snpmi_grm_begin)");
+}
+static void session_check_dtype(int dtype) {
+    session_check_open();
+    SNPMI_REQUIRE(g_session.dtype == dtype, SNPMI_E_ARG, "dtype differs from snpmi_grm_begin");
+}
+static void session_check_iids(uint64_t n) {
+    SNPMI_REQUIRE(n == g_session.n, SNPMI_E_ARG, "iid count differs from snpmi_grm_begin");
+}
+static void session_check(int dtype, uint64_t n) {
+    session_check_dtype(dtype);
+    session_check_iids(n);
+}
+template <typename T>
+static void session_check(uint64_t n) {
+    session_check(DT<T>::v, n);
+}
+
+// The argument checks several entry points share; a site whose text has always differed passes it.
+static bool part_ok(int rank, int world) { return world >= 1 && rank >= 0 && rank < world; }
+static void check_part(int rank, int world, const char* msg = "bad partition") {
+    SNPMI_REQUIRE(part_ok(rank, world), SNPMI_E_ARG, msg);
+}
+static void check_pitch(uint64_t pitch, uint64_t n, const char* msg = "pitch must be snpmi_packed_pitch") {
+    SNPMI_REQUIRE(pitch % 64 == 0 && pitch >= ceil_div(n, 4), SNPMI_E_ARG, msg);
 }
 
 // supertile block order of the dense fp16x2 SYRK, kept on the device per (nb, xcd); built once
@@ -1135,21 +1160,28 @@ static T* dense_upload(Device& d, const T* val, uint64_t rows, uint64_t cols, in
     return Z;
 }
 
+// Standardize the F-order operand Z in place with host stats [cols][2]: sent first if given, brought
+// back if computed (enqueued; the caller synchronises).  standardize_impl keeps its own sequence:
+// its value copy-out sits between the launch and the stats copy.
+static void dense_standardize(Device& d, void* Z, uint64_t rows, uint64_t cols, uint64_t ldz, int dtype,
+                              const StdArgs& sa, void* stats) {
+    const size_t sb = cols * 2 * dtype_size(dtype);
+    void* ds = d.get(Device::S_STATS, sb);
+    if (sa.use_stats) SNPMI_HIP(hipMemcpyAsync(ds, stats, sb, hipMemcpyHostToDevice, d.stream));
+    launch_dense_standardize(Z, rows, cols, ldz, 0, dtype, sa, ds, d.stream);
+    if (!sa.use_stats) SNPMI_HIP(hipMemcpyAsync(stats, ds, sb, hipMemcpyDeviceToHost, d.stream));
+}
+
 template <typename T>
-static void grm_dense_impl(const T* val, uint64_t rows, uint64_t cols, int order_c, int std_kind, double a, double b,
-                           int use_stats, T* stats, int diag_k_to_n, double* factor, T* K_out) {
+static void grm_dense_impl(const T* val, uint64_t rows, uint64_t cols, int order_c, const StdArgs& sa, T* stats,
+                           int diag_k_to_n, double* factor, T* K_out) {
     std::lock_guard<std::recursive_mutex> lk(g_call_mutex);
     SNPMI_REQUIRE(K_out != nullptr || rows == 0, SNPMI_E_ARG, "K_out is NULL");
     Device& d = device();
     const int dt = DT<T>::v;
     uint64_t ldz = 0;
     T* Z = dense_upload(d, val, rows, cols, order_c, &ldz);
-    if (std_kind != SNPMI_STD_NONE && cols > 0) {
-        T* ds = (T*)d.get(Device::S_STATS, cols * 2 * sizeof(T));
-        if (use_stats) SNPMI_HIP(hipMemcpyAsync(ds, stats, cols * 2 * sizeof(T), hipMemcpyHostToDevice, d.stream));
-        launch_dense_standardize(Z, rows, cols, ldz, 0, dt, std_kind, a, b, use_stats, ds, d.stream);
-        if (!use_stats) SNPMI_HIP(hipMemcpyAsync(stats, ds, cols * 2 * sizeof(T), hipMemcpyDeviceToHost, d.stream));
-    }
+    if (sa.kind != SNPMI_STD_NONE && cols > 0) dense_standardize(d, Z, rows, cols, ldz, dt, sa, stats);
     const uint64_t tile_bytes = n_tiles_upper(rows) * kTile * kTile * sizeof(T);
     T* tiles = (T*)d.get(Device::S_TILES, tile_bytes);
     if (rows > 0) syrk_dense_auto(d, Z, ldz, rows, cols, dt, tiles, 0);
@@ -1214,9 +1246,7 @@ static void snp_scale_impl(T* val, uint64_t count, double rows, int scale_only, 
 template <typename T>
 static void grm_add_dense_impl(const T* val, uint64_t rows, uint64_t cols, int order_c) {
     std::lock_guard<std::recursive_mutex> lk(g_call_mutex);
-    SNPMI_REQUIRE(g_session.active, SNPMI_E_ARG, "no GRM session (call snpmi_grm_begin)");
-    SNPMI_REQUIRE(g_session.dtype == DT<T>::v, SNPMI_E_ARG, "dtype differs from snpmi_grm_begin");
-    SNPMI_REQUIRE(rows == g_session.n, SNPMI_E_ARG, "iid count differs from snpmi_grm_begin");
+    session_check<T>(rows);
     SNPMI_REQUIRE(val != nullptr || rows == 0 || cols == 0, SNPMI_E_ARG, "val is NULL");
     if (rows == 0 || cols == 0) return;
     Device& d = device();
@@ -1231,36 +1261,26 @@ static void grm_add_dense_impl(const T* val, uint64_t rows, uint64_t cols, int o
 // dist.hip (snpmi_grm_add_dist_*): the session's operand buffer, and the add of a block converted
 // into it -- grm_dense_impl's standardize + SYRK on the session's tiles
 void* grm_session_operand(int dtype, uint64_t rows, uint64_t cols, uint64_t* ldz) {
-    SNPMI_REQUIRE(g_session.active, SNPMI_E_ARG, "no GRM session (call snpmi_grm_begin)");
-    SNPMI_REQUIRE(g_session.dtype == dtype, SNPMI_E_ARG, "dtype differs from snpmi_grm_begin");
-    SNPMI_REQUIRE(rows == g_session.n, SNPMI_E_ARG, "iid count differs from snpmi_grm_begin");
+    session_check(dtype, rows);
     *ldz = round_up(std::max<uint64_t>(rows, 1), 256);
     return device().get(Device::S_DENSE, *ldz * std::max<uint64_t>(cols, 1) * dtype_size(dtype));
 }
 
-void grm_session_add_operand(int dtype, void* Z, uint64_t ldz, uint64_t cols, int std_kind, double a, double b,
-                             int use_stats, void* stats) {
+void grm_session_add_operand(int dtype, void* Z, uint64_t ldz, uint64_t cols, const StdArgs& sa, void* stats) {
     Device& d = device();
     const uint64_t n = g_session.n;
-    if (std_kind != SNPMI_STD_NONE) {
-        const size_t sb = cols * 2 * dtype_size(dtype);
-        void* ds = d.get(Device::S_STATS, sb);
-        if (use_stats) SNPMI_HIP(hipMemcpyAsync(ds, stats, sb, hipMemcpyHostToDevice, d.stream));
-        launch_dense_standardize(Z, n, cols, ldz, 0, dtype, std_kind, a, b, use_stats, ds, d.stream);
-        if (!use_stats) SNPMI_HIP(hipMemcpyAsync(stats, ds, sb, hipMemcpyDeviceToHost, d.stream));
-    }
+    if (sa.kind != SNPMI_STD_NONE) dense_standardize(d, Z, n, cols, ldz, dtype, sa, stats);
     syrk_dense_auto(d, Z, ldz, n, cols, dtype, session_tiles(d), g_session.wrote ? 1 : 0);
     g_session.wrote = true;
     SNPMI_HIP(hipStreamSynchronize(d.stream));
 }
 
-// Packed SNP columns already in HBM ([m][pitch] bytes, every iid of the reader): the argument checks
-// every add of them shares, their chunks and the per-chunk stats + LUT.
-template <typename T>
-static void check_packed_args(uint64_t pitch, uint64_t n, uint64_t m, int std_kind, const T* stats) {
-    SNPMI_REQUIRE(pitch % 64 == 0 && pitch >= ceil_div(n, 4), SNPMI_E_ARG, "pitch must be snpmi_packed_pitch");
-    SNPMI_REQUIRE(std_kind >= SNPMI_STD_NONE && std_kind <= SNPMI_STD_BETA, SNPMI_E_ARG, "bad standardizer kind");
-    SNPMI_REQUIRE(stats != nullptr || std_kind == SNPMI_STD_NONE || m == 0, SNPMI_E_ARG, "stats is NULL");
+// Packed SNP columns already in HBM (PackedSnps: [m][pitch] bytes, every iid of the reader): the
+// argument checks every add of them shares, their chunks and the per-chunk stats + LUT.
+static void check_packed_args(const PackedSnps& ps, const StdArgs& sa, const void* stats) {
+    check_pitch(ps.pitch, ps.n);
+    SNPMI_REQUIRE(sa.kind >= SNPMI_STD_NONE && sa.kind <= SNPMI_STD_BETA, SNPMI_E_ARG, "bad standardizer kind");
+    SNPMI_REQUIRE(stats != nullptr || sa.kind == SNPMI_STD_NONE || ps.m == 0, SNPMI_E_ARG, "stats is NULL");
 }
 // equal chunks of <= 2^16 SNPs (the int32 / CRT accumulation cap), multiples of 256
 static uint64_t packed_chunk_snps(uint64_t m) {
@@ -1272,23 +1292,23 @@ static uint64_t packed_chunk_snps(uint64_t m) {
 // (the reference's block_size bounds host memory, snpreader.py:651).  stats may be host memory
 // (copied synchronously) or device memory (the call then only enqueues).
 template <typename T, class Mul>
-static void for_packed_chunks(Device& d, const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, int count_a1,
-                              int std_kind, double a, double b, int use_stats, T* stats, Mul&& mul) {
-    if (m == 0 || n == 0) return;
-    SNPMI_REQUIRE(packed != nullptr && is_device_ptr(d, packed), SNPMI_E_ARG,
+static void for_packed_chunks(Device& d, const PackedSnps& ps, const StdArgs& sa, T* stats, Mul&& mul) {
+    const uint64_t m = ps.m;
+    if (m == 0 || ps.n == 0) return;
+    SNPMI_REQUIRE(ps.P != nullptr && is_device_ptr(d, ps.P), SNPMI_E_ARG,
                   "packed must be device memory of the current device");
-    const bool host_stats = stats && std_kind != SNPMI_STD_NONE && !is_device_ptr(d, stats);
+    const bool host_stats = stats && sa.kind != SNPMI_STD_NONE && !is_device_ptr(d, stats);
     const uint64_t step = packed_chunk_snps(m);
     for (uint64_t s0 = 0; s0 < m; s0 += step) {
         const uint64_t cnt = std::min(step, m - s0);
-        const uint8_t* src = packed + s0 * pitch;
+        const uint8_t* src = ps.P + s0 * ps.pitch;
         T* lut = (T*)d.get(Device::S_LUT, cnt * 4 * sizeof(T));
         T* st = (stats && !host_stats) ? stats + 2 * s0 : (T*)d.get(Device::S_STATS, cnt * 2 * sizeof(T));
-        if (host_stats && use_stats)
+        if (host_stats && sa.use_stats)
             SNPMI_HIP(hipMemcpyAsync(st, stats + 2 * s0, cnt * 2 * sizeof(T), hipMemcpyHostToDevice, d.stream));
-        launch_snp_stats(src, pitch, n, cnt, count_a1, std_kind, a, b, use_stats, DT<T>::v, st, lut, d.stream);
+        launch_snp_stats(src, ps.pitch, ps.n, cnt, ps.count_a1, sa, DT<T>::v, st, lut, d.stream);
         mul(src, cnt, (const T*)lut, s0 + cnt == m);
-        if (host_stats && !use_stats) {
+        if (host_stats && !sa.use_stats) {
             SNPMI_HIP(hipMemcpyAsync(stats + 2 * s0, st, cnt * 2 * sizeof(T), hipMemcpyDeviceToHost, d.stream));
             SNPMI_HIP(hipStreamSynchronize(d.stream));  // S_STATS is reused by the next chunk
         }
@@ -1297,13 +1317,10 @@ static void for_packed_chunks(Device& d, const uint8_t* packed, uint64_t pitch, 
 }
 
 template <typename T>
-static void check_session_packed(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, int std_kind,
-                                 const T* stats) {
-    SNPMI_REQUIRE(g_session.active, SNPMI_E_ARG, "no GRM session (call snpmi_grm_begin)");
-    SNPMI_REQUIRE(g_session.dtype == DT<T>::v, SNPMI_E_ARG, "dtype differs from snpmi_grm_begin");
-    SNPMI_REQUIRE(n == g_session.n, SNPMI_E_ARG, "iid count differs from snpmi_grm_begin");
-    check_packed_args(pitch, n, m, std_kind, stats);
-    SNPMI_REQUIRE(packed != nullptr || m == 0 || n == 0, SNPMI_E_ARG, "packed is NULL");
+static void check_session_packed(const PackedSnps& ps, const StdArgs& sa, const T* stats) {
+    session_check<T>(ps.n);
+    check_packed_args(ps, sa, stats);
+    SNPMI_REQUIRE(ps.P != nullptr || ps.m == 0 || ps.n == 0, SNPMI_E_ARG, "packed is NULL");
 }
 // one chunk into the session's tiles
 template <typename T>
@@ -1315,15 +1332,13 @@ static void session_add_chunk(Device& d, const uint8_t* src, uint64_t pitch, uin
 
 // the chunks added to the session
 template <typename T>
-static void grm_add_packed_impl(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, int count_a1,
-                                int std_kind, double a, double b, int use_stats, T* stats) {
+static void grm_add_packed_impl(const PackedSnps& ps, const StdArgs& sa, T* stats) {
     std::lock_guard<std::recursive_mutex> lk(g_call_mutex);
-    check_session_packed(packed, pitch, n, m, std_kind, stats);
+    check_session_packed(ps, sa, stats);
     Device& d = device();
-    for_packed_chunks(d, packed, pitch, n, m, count_a1, std_kind, a, b, use_stats, stats,
-                      [&](const uint8_t* src, uint64_t cnt, const T* lut, bool) {
-                          session_add_chunk(d, src, pitch, cnt, lut);
-                      });
+    for_packed_chunks(d, ps, sa, stats, [&](const uint8_t* src, uint64_t cnt, const T* lut, bool) {
+        session_add_chunk(d, src, ps.pitch, cnt, lut);
+    });
 }
 // Column groups of the upper triangle for an overlapped collective: ranges [L0, L1) of 256-block
 // indices covering whole supertile columns (16 block columns).  The last group holds ~1/4 of the
@@ -1533,8 +1548,7 @@ static void session_sum_planned(Device& d, int collective, int rt, int parts, hi
 
 template <typename T>
 static void check_reduce_args(int collective, int parts) {
-    SNPMI_REQUIRE(g_session.active, SNPMI_E_ARG, "no GRM session (call snpmi_grm_begin)");
-    SNPMI_REQUIRE(g_session.dtype == DT<T>::v, SNPMI_E_ARG, "dtype differs from snpmi_grm_begin");
+    session_check_dtype(DT<T>::v);
     SNPMI_REQUIRE(collective >= 0 && collective <= 2, SNPMI_E_ARG, "collective must be 0 (none), 1 (reduce), 2 (all-reduce)");
     SNPMI_REQUIRE(collective == 0 || rccl_ready(), SNPMI_E_ARG, "RCCL communicator not initialised");
     SNPMI_REQUIRE(parts >= 1, SNPMI_E_ARG, "parts must be >= 1");
@@ -1544,57 +1558,51 @@ static void check_reduce_args(int collective, int parts) {
 // the last SNP chunk of for_packed_chunks runs through grouped_reduce_f32 /
 // crt_reduce_f64.  Host stats, or a path without groups, add first and sum after.
 template <typename T>
-static void grm_add_packed_reduce_impl(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, int count_a1,
-                                       int std_kind, double a, double b, int use_stats, T* stats, int collective,
-                                       int root, int parts, hipEvent_t syrk_done) {
+static void grm_add_packed_reduce_impl(const PackedSnps& ps, const StdArgs& sa, T* stats, int collective, int root,
+                                       int parts, hipEvent_t syrk_done) {
     std::lock_guard<std::recursive_mutex> lk(g_call_mutex);
     check_reduce_args<T>(collective, parts);
     Device& d = device();
     const int rt = collective == 1 ? root : -1;
-    const bool grouped = m > 0 && n > 0 && n == g_session.n && sum_plan(d, n, DT<T>::v, parts).grouped &&
-                         (std_kind == SNPMI_STD_NONE || (stats && is_device_ptr(d, stats)));
+    const uint64_t n = ps.n, pitch = ps.pitch;
+    const bool grouped = ps.m > 0 && n > 0 && n == g_session.n && sum_plan(d, n, DT<T>::v, parts).grouped &&
+                         (sa.kind == SNPMI_STD_NONE || (stats && is_device_ptr(d, stats)));
     g_last_groups = 1;
     if (!grouped) {
-        grm_add_packed_impl<T>(packed, pitch, n, m, count_a1, std_kind, a, b, use_stats, stats);
+        grm_add_packed_impl<T>(ps, sa, stats);
         session_sum_planned<T>(d, collective, rt, parts, syrk_done);
         return;
     }
-    check_packed_args(pitch, n, m, std_kind, stats);
-    for_packed_chunks(d, packed, pitch, n, m, count_a1, std_kind, a, b, use_stats, stats,
-                      [&](const uint8_t* src, uint64_t cnt, const T* lut, bool last) {
-                          if (!last) return session_add_chunk(d, src, pitch, cnt, lut);
-                          T* tiles = (T*)session_tiles(d);
-                          const int acc = g_session.wrote ? 1 : 0;
-                          g_session.wrote = true;
-                          if constexpr (std::is_same<T, double>::value)
-                              g_last_groups = crt_reduce_f64(d, src, pitch, n, cnt, lut, tiles, acc, collective, rt,
-                                                             syrk_done);
-                          else
-                              g_last_groups = grouped_reduce_f32(d, src, pitch, n, cnt, lut, tiles, acc, collective, rt,
-                                                                 parts, syrk_done);
-                      });
+    check_packed_args(ps, sa, stats);
+    for_packed_chunks(d, ps, sa, stats, [&](const uint8_t* src, uint64_t cnt, const T* lut, bool last) {
+        if (!last) return session_add_chunk(d, src, pitch, cnt, lut);
+        T* tiles = (T*)session_tiles(d);
+        const int acc = g_session.wrote ? 1 : 0;
+        g_session.wrote = true;
+        if constexpr (std::is_same<T, double>::value)
+            g_last_groups = crt_reduce_f64(d, src, pitch, n, cnt, lut, tiles, acc, collective, rt, syrk_done);
+        else
+            g_last_groups = grouped_reduce_f32(d, src, pitch, n, cnt, lut, tiles, acc, collective, rt, parts, syrk_done);
+    });
 }
 
 // snpmi_grm_add_bed_{f32,f64} (the session's last add: a rank's SNP span of a .bed) + the K-tile
 // collective, overlapped the same way on the file stream's last chunk.
 template <typename T>
-static void grm_add_bed_reduce_impl(const char* path, uint64_t n_iid, uint64_t n_sid, int count_a1,
-                                    const uint64_t* iid_idx, uint64_t n_out_iid, const uint64_t* sid_idx,
-                                    uint64_t n_out_sid, int std_kind, double a, double b, int use_stats, T* stats,
-                                    int num_threads, int collective, int root, int parts) {
+static void grm_add_bed_reduce_impl(const BedSel& s, const StdArgs& sa, T* stats, int collective, int root,
+                                    int parts) {
     std::lock_guard<std::recursive_mutex> lk(g_call_mutex);
     check_reduce_args<T>(collective, parts);
-    SNPMI_REQUIRE((iid_idx ? n_out_iid : n_iid) == g_session.n, SNPMI_E_ARG, "iid count differs from snpmi_grm_begin");
+    session_check_iids(s.n_out);
     Device& d = device();
     const int rt = collective == 1 ? root : -1;
-    const uint64_t n = g_session.n, total = sid_idx ? n_out_sid : n_sid;
+    const uint64_t n = g_session.n, total = s.m_out;
     T* tiles = (T*)session_tiles(d);
     uint64_t done = 0;
     int groups = 1;
     const SumPlan plan = sum_plan(d, n, DT<T>::v, parts);
     const bool wrote = grm_stream_bed<T>(
-        d, !g_session.wrote, path, n_iid, n_sid, count_a1, iid_idx, n_out_iid, sid_idx, n_out_sid, std_kind, a, b,
-        use_stats, stats, num_threads,
+        d, !g_session.wrote, s, sa, stats,
         [&](const uint8_t* packed, uint64_t pitch, uint64_t nn, uint64_t cnt, const T* lut, bool acc) {
             done += cnt;
             const bool last = done == total;
@@ -1813,37 +1821,137 @@ static void rect_add_chunk(Device& d, const RectAdd& a, const uint8_t* packed, u
 }
 
 template <typename T>
-static void rect_add_packed_impl(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, int count_a1,
-                                 int std_kind, double a, double b, int use_stats, T* stats, const uint64_t* row_idx,
+static void rect_add_packed_impl(const PackedSnps& ps, const StdArgs& sa, T* stats, const uint64_t* row_idx,
                                  const uint64_t* col_idx) {
     std::lock_guard<std::recursive_mutex> lk(g_call_mutex);
-    rect_check_session<T>(n, row_idx, col_idx);
-    check_packed_args(pitch, n, m, std_kind, stats);
+    rect_check_session<T>(ps.n, row_idx, col_idx);
+    check_packed_args(ps, sa, stats);
     Device& d = device();
-    const RectAdd ra = rect_add_begin<T>(d, n, row_idx, col_idx);
+    const RectAdd ra = rect_add_begin<T>(d, ps.n, row_idx, col_idx);
     // the chunks of snpmi_grm_add_packed_*: the same launch boundaries as the whole-K session
-    for_packed_chunks(d, packed, pitch, n, m, count_a1, std_kind, a, b, use_stats, stats,
-                      [&](const uint8_t* src, uint64_t cnt, const T* lut, bool) {
-                          rect_add_chunk<T>(d, ra, src, pitch, cnt, lut);
-                      });
-    if (m > 0 && n > 0) SNPMI_HIP(hipStreamSynchronize(d.stream));
+    for_packed_chunks(d, ps, sa, stats, [&](const uint8_t* src, uint64_t cnt, const T* lut, bool) {
+        rect_add_chunk<T>(d, ra, src, ps.pitch, cnt, lut);
+    });
+    if (ps.m > 0 && ps.n > 0) SNPMI_HIP(hipStreamSynchronize(d.stream));
 }
 
 template <typename T>
-static void rect_add_bed_impl(const char* path, uint64_t n_iid, uint64_t n_sid, int count_a1, const uint64_t* iid_idx,
-                              uint64_t n_out_iid, const uint64_t* sid_idx, uint64_t n_out_sid, int std_kind, double a,
-                              double b, int use_stats, T* stats, int num_threads, const uint64_t* row_idx,
+static void rect_add_bed_impl(const BedSel& s, const StdArgs& sa, T* stats, const uint64_t* row_idx,
                               const uint64_t* col_idx) {
     std::lock_guard<std::recursive_mutex> lk(g_call_mutex);
-    const uint64_t n = iid_idx ? n_out_iid : n_iid;
-    rect_check_session<T>(n, row_idx, col_idx);
+    rect_check_session<T>(s.n_out, row_idx, col_idx);
     Device& d = device();
-    const RectAdd ra = rect_add_begin<T>(d, n, row_idx, col_idx);
-    grm_stream_bed<T>(d, false, path, n_iid, n_sid, count_a1, iid_idx, n_out_iid, sid_idx, n_out_sid, std_kind, a, b,
-                      use_stats, stats, num_threads,
+    const RectAdd ra = rect_add_begin<T>(d, s.n_out, row_idx, col_idx);
+    grm_stream_bed<T>(d, false, s, sa, stats,
                       [&](const uint8_t* packed, uint64_t pitch, uint64_t nn, uint64_t cnt, const T* lut, bool) {
                           rect_add_chunk<T>(d, ra, packed, pitch, cnt, lut);
                       });
+}
+
+// ---------------------------------------------------------------------- partitioned GRM (cfg5)
+// K too large to replicate: part `rank` of `world` owns the 256x256 blocks of its layout table
+// (syrk.hip part_layout, part_tables above) and nothing else of K.
+
+// host copy of the last part layout asked for (snpmi_grm_part_coords is called per block)
+static std::mutex g_layout_mutex;
+static std::vector<uint32_t> g_layout;
+static uint64_t g_layout_key[3] = {~0ull, 0, 0};
+static const std::vector<uint32_t>& host_layout(uint64_t nb, int rank, int world) {
+    if (g_layout_key[0] != nb || g_layout_key[1] != (uint64_t)rank || g_layout_key[2] != (uint64_t)world) {
+        part_layout(nb, rank, world, g_layout);
+        g_layout_key[0] = nb;
+        g_layout_key[1] = (uint64_t)rank;
+        g_layout_key[2] = (uint64_t)world;
+    }
+    return g_layout;
+}
+
+// From a file: rank part_rank of part_world streams EVERY SNP of the .bed (stats need all iids of
+// a SNP; each rank computes them itself -- no exchange) and accumulates only its own blocks
+// (snpmi_grm_part_coords) in HBM, then copies them to blocks_out (n_local x 65536 values,
+// row-major blocks; may be a memory-mapped file).
+template <typename T>
+static void grm_part_bed_impl(const BedSel& s, const StdArgs& sa, T* stats, int part_rank, int part_world,
+                              T* blocks_out) {
+    std::lock_guard<std::recursive_mutex> lk(g_call_mutex);
+    check_part(part_rank, part_world, "bad rank / world");
+    const uint64_t nloc = grm_part_blocks(s.n_out, part_rank, part_world);
+    SNPMI_REQUIRE(blocks_out != nullptr || nloc == 0, SNPMI_E_ARG, "blocks_out is NULL");
+    Device& d = device();
+    const uint64_t bytes = std::max<uint64_t>(nloc, 1) * 256 * 256 * sizeof(T);
+    // blocks_out in device memory: the SYRK accumulates into it directly (K stays in HBM, no
+    // scratch, no copy-out); host memory: scratch tiles + a pinned-bounce copy at the end
+    const bool dev_out = nloc && is_device_ptr(d, blocks_out);
+    T* blocks = dev_out ? blocks_out : (T*)d.get(Device::S_TILES, bytes);
+    const bool wrote = grm_stream_bed<T>(
+        d, true, s, sa, stats,
+        [&](const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t cnt, const T* lut, bool acc) {
+            syrk_packed_auto(d, packed, pitch, n, cnt, lut, DT<T>::v, part_dest(blocks, n, part_rank, part_world), acc);
+        });
+    if (!wrote) SNPMI_HIP(hipMemsetAsync(blocks, 0, dev_out ? nloc * 256 * 256 * sizeof(T) : bytes, d.stream));
+    const size_t bb = 256 * 256 * sizeof(T);  // one block per "row" of the pinned-bounce copy
+    if (nloc && !dev_out) d2h_rows(d, blocks_out, bb, blocks, bb, bb, nloc, resolve_threads(s.num_threads));
+    SNPMI_HIP(hipStreamSynchronize(d.stream));
+}
+
+// snpmi_dev_syrk_packed_part{,_f64}: one SNP block already in HBM into a part's blocks
+static void dev_syrk_packed_part(int dtype, const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m,
+                                 const void* lut, int part_rank, int part_world, void* blocks, int accumulate) {
+    std::lock_guard<std::recursive_mutex> lk(g_call_mutex);  // shared scratch slots
+    check_part(part_rank, part_world);
+    check_pitch(pitch, n);
+    syrk_packed_auto(device(), packed, pitch, n, m, lut, dtype, part_dest(blocks, n, part_rank, part_world), accumulate);
+}
+
+// K[ri, ci] restricted to part `part_rank`'s blocks (the rest 0): the parts' outputs summed over
+// the ranks are the sub-matrix (snpmi_grm_part_extract_*, the PartitionedKernel reader)
+template <typename T>
+static void part_extract_impl(const T* blocks, uint64_t n, int part_rank, int part_world, const uint64_t* ri,
+                              uint64_t nr, const uint64_t* ci, uint64_t nc, int order_c, double scale, T* out) {
+    std::lock_guard<std::recursive_mutex> lk(g_call_mutex);
+    check_part(part_rank, part_world);
+    SNPMI_REQUIRE(out != nullptr || nr * nc == 0, SNPMI_E_ARG, "out is NULL");
+    Device& d = device();
+    const uint64_t nloc = grm_part_blocks(n, part_rank, part_world);
+    SNPMI_REQUIRE(nloc == 0 || (blocks && is_device_ptr(d, blocks)), SNPMI_E_ARG,
+                  "blocks must be device memory of the current device");
+    for (uint64_t k = 0; ri && k < nr; k++) SNPMI_REQUIRE(ri[k] < n, SNPMI_E_INDEX, "iid0 index out of range");
+    for (uint64_t k = 0; ci && k < nc; k++) SNPMI_REQUIRE(ci[k] < n, SNPMI_E_INDEX, "iid1 index out of range");
+    SNPMI_REQUIRE(ri || nr <= n, SNPMI_E_INDEX, "iid0 count exceeds n");
+    SNPMI_REQUIRE(ci || nc <= n, SNPMI_E_INDEX, "iid1 count exceeds n");
+    if (nr * nc == 0) return;
+    const PartTables pt = part_tables(ceil_div(n, 256), part_rank, part_world);
+    uint64_t* dri = nullptr;
+    uint64_t* dci = nullptr;
+    if (ri) {
+        dri = (uint64_t*)d.get(Device::S_IDX, nr * 8);
+        SNPMI_HIP(hipMemcpyAsync(dri, ri, nr * 8, hipMemcpyHostToDevice, d.stream));
+    }
+    if (ci) {
+        dci = (uint64_t*)d.get(Device::S_IDX2, nc * 8);
+        SNPMI_HIP(hipMemcpyAsync(dci, ci, nc * 8, hipMemcpyHostToDevice, d.stream));
+    }
+    const bool dev = is_device_ptr(d, out);
+    T* o = dev ? out : (T*)d.get(Device::S_K, nr * nc * sizeof(T));
+    launch_part_extract(blocks, pt.lslot, DT<T>::v, dri, nr, dci, nc, order_c, scale, o, d.stream);
+    if (!dev) SNPMI_HIP(hipMemcpyAsync(out, o, nr * nc * sizeof(T), hipMemcpyDeviceToHost, d.stream));
+    SNPMI_HIP(hipStreamSynchronize(d.stream));
+}
+
+template <typename T>
+static void part_trace_impl(const T* blocks, uint64_t n, int part_rank, int part_world, double* trace) {
+    std::lock_guard<std::recursive_mutex> lk(g_call_mutex);
+    check_part(part_rank, part_world);
+    SNPMI_REQUIRE(trace != nullptr, SNPMI_E_ARG, "trace is NULL");
+    Device& d = device();
+    *trace = 0.0;
+    if (n == 0 || grm_part_blocks(n, part_rank, part_world) == 0) return;
+    SNPMI_REQUIRE(blocks && is_device_ptr(d, blocks), SNPMI_E_ARG, "blocks must be device memory of the current device");
+    const PartTables pt = part_tables(ceil_div(n, 256), part_rank, part_world);
+    double* tr = (double*)d.get(Device::S_RED, 64);
+    launch_part_trace(blocks, pt.dslot, n, DT<T>::v, tr, d.stream);
+    SNPMI_HIP(hipMemcpyAsync(trace, tr, 8, hipMemcpyDeviceToHost, d.stream));
+    SNPMI_HIP(hipStreamSynchronize(d.stream));
 }
 }  // namespace snpmi
 
@@ -1999,6 +2107,19 @@ int snpmi_get_kernel_variant(const char* kernel, int* variant) {
     });
 }
 
+// The ABI spells a .bed selection, packed SNPs in HBM and the standardizer settings as loose
+// parameters, under the same names in every entry point (include/snpmi.h).  The parameter lists,
+// and the blocks built from them at this boundary:
+#define SNPMI_BED_PARAMS                                                                             \
+    const char* path, uint64_t n_iid, uint64_t n_sid, int count_a1, const uint64_t* iid_idx, uint64_t n_out_iid, \
+        const uint64_t* sid_idx, uint64_t n_out_sid
+#define SNPMI_BED_SEL bed_sel(path, n_iid, n_sid, count_a1, iid_idx, n_out_iid, sid_idx, n_out_sid, num_threads)
+#define SNPMI_PACKED_PARAMS const uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_t n_sid, int count_a1
+#define SNPMI_PACKED_SNPS (PackedSnps{{packed, pitch, n_iid}, n_sid, count_a1})
+#define SNPMI_STD_PARAMS(T) int std_kind, double a, double b, int use_stats, T* stats
+#define SNPMI_STD_ARGS (StdArgs{std_kind, a, b, use_stats})
+// Entry points whose _f32 / _f64 (/ _i8) forms differ only in the value type come from one macro.
+
 int snpmi_bed_check(const char* path, uint64_t n_iid, uint64_t n_sid) {
     return guarded([&] {
         BedMap m;
@@ -2007,12 +2128,10 @@ int snpmi_bed_check(const char* path, uint64_t n_iid, uint64_t n_sid) {
 }
 
 #define SNPMI_BED_READ(SUFFIX, T)                                                                                  \
-    int snpmi_bed_read_##SUFFIX(const char* path, uint64_t n_iid, uint64_t n_sid, int count_a1,                  \
-                                const uint64_t* iid_idx, uint64_t n_out_iid, const uint64_t* sid_idx,             \
-                                uint64_t n_out_sid, int order_c, T* out, int num_threads) {                       \
+    int snpmi_bed_read_##SUFFIX(SNPMI_BED_PARAMS, int order_c, T* out, int num_threads) {                          \
         return guarded([&] {                                                                                       \
-            bed_read_impl<T>(path, n_iid, n_sid, count_a1, iid_idx, n_out_iid, sid_idx, n_out_sid, order_c,       \
-                             SNPMI_STD_NONE, 0.0, 0.0, 0, (T*)nullptr, out, num_threads);                         \
+            bed_read_impl<T>(SNPMI_BED_SEL, order_c, {SNPMI_STD_NONE, 0.0, 0.0, 0}, (T*)nullptr, out,              \
+                             n_out_iid == 0 || n_out_sid == 0);                                                    \
         });                                                                                                        \
     }
 SNPMI_BED_READ(f32, float)
@@ -2020,14 +2139,12 @@ SNPMI_BED_READ(f64, double)
 SNPMI_BED_READ(i8, int8_t)
 
 #define SNPMI_BED_READ_STD(SUFFIX, T)                                                                              \
-    int snpmi_bed_read_standardize_##SUFFIX(const char* path, uint64_t n_iid, uint64_t n_sid, int count_a1,      \
-                                            const uint64_t* iid_idx, uint64_t n_out_iid, const uint64_t* sid_idx, \
-                                            uint64_t n_out_sid, int order_c, int std_kind, double a, double b,    \
-                                            int use_stats, T* stats, T* out, int num_threads) {                   \
+    int snpmi_bed_read_standardize_##SUFFIX(SNPMI_BED_PARAMS, int order_c, SNPMI_STD_PARAMS(T), T* out,            \
+                                            int num_threads) {                                                     \
         return guarded([&] {                                                                                       \
             SNPMI_REQUIRE(std_kind == SNPMI_STD_NONE || stats != nullptr, SNPMI_E_ARG, "stats is NULL");          \
-            bed_read_impl<T>(path, n_iid, n_sid, count_a1, iid_idx, n_out_iid, sid_idx, n_out_sid, order_c,       \
-                             std_kind, a, b, use_stats, stats, out, num_threads);                                 \
+            bed_read_impl<T>(SNPMI_BED_SEL, order_c, SNPMI_STD_ARGS, stats, out,                                   \
+                             n_out_iid == 0 || n_out_sid == 0);                                                    \
         });                                                                                                        \
     }
 SNPMI_BED_READ_STD(f32, float)
@@ -2046,7 +2163,7 @@ int snpmi_dev_encode(const void* val, int dtype, int order_c, uint64_t ld, uint6
                      int count_a1, uint8_t* packed, uint64_t pitch, uint64_t* bad_values) {
     return guarded([&] {
         std::lock_guard<std::recursive_mutex> lk(g_call_mutex);  // shared scratch slots
-        SNPMI_REQUIRE(pitch % 64 == 0 && pitch >= ceil_div(n_iid, 4), SNPMI_E_ARG, "pitch must be a multiple of 64 >= ceil(n/4)");
+        check_pitch(pitch, n_iid, "pitch must be a multiple of 64 >= ceil(n/4)");
         SNPMI_REQUIRE(order_c || ld % 16 == 0, SNPMI_E_ARG, "F-order ld must be a multiple of 16");
         SNPMI_REQUIRE(order_c ? ld >= n_sid : ld >= n_iid, SNPMI_E_ARG, "ld too small");
         Device& d = device();
@@ -2072,86 +2189,45 @@ int snpmi_grm_begin(uint64_t n_out_iid, int dtype) {
     });
 }
 
-#define SNPMI_GRM_ADD(SUFFIX, T, DTV)                                                                               \
-    int snpmi_grm_add_bed_##SUFFIX(const char* path, uint64_t n_iid, uint64_t n_sid, int count_a1,                 \
-                                   const uint64_t* iid_idx, uint64_t n_out_iid, const uint64_t* sid_idx,            \
-                                   uint64_t n_out_sid, int std_kind, double a, double b, int use_stats, T* stats,   \
-                                   int num_threads) {                                                                \
+// PARTS: the one thing the pair differs in -- the f64 reduce forms take parts < 1 as 1 (the CRT
+// path's own residue chunks are the groups), the f32 forms reject it
+#define SNPMI_GRM_ADD(SUFFIX, T, PARTS)                                                                             \
+    int snpmi_grm_add_bed_##SUFFIX(SNPMI_BED_PARAMS, SNPMI_STD_PARAMS(T), int num_threads) {                        \
         return guarded([&] {                                                                                         \
             std::lock_guard<std::recursive_mutex> lk(g_call_mutex);                                                  \
-            SNPMI_REQUIRE(g_session.active, SNPMI_E_ARG, "no GRM session (call snpmi_grm_begin)");                  \
-            SNPMI_REQUIRE(g_session.dtype == DTV, SNPMI_E_ARG, "dtype differs from snpmi_grm_begin");               \
-            SNPMI_REQUIRE((iid_idx ? n_out_iid : n_iid) == g_session.n, SNPMI_E_ARG,                                \
-                          "iid count differs from snpmi_grm_begin");                                                 \
+            const BedSel s = SNPMI_BED_SEL;                                                                          \
+            session_check<T>(s.n_out);                                                                               \
             Device& d = device();                                                                                    \
             T* tiles = (T*)session_tiles(d);                                                                         \
-            if (grm_add_bed<T>(d, tiles, !g_session.wrote, path, n_iid, n_sid, count_a1, iid_idx, n_out_iid,        \
-                               sid_idx, n_out_sid, std_kind, a, b, use_stats, stats, num_threads))                   \
-                g_session.wrote = true;                                                                              \
+            if (grm_add_bed<T>(d, tiles, !g_session.wrote, s, SNPMI_STD_ARGS, stats)) g_session.wrote = true;        \
         });                                                                                                          \
+    }                                                                                                                \
+    int snpmi_grm_add_bed_reduce_##SUFFIX(SNPMI_BED_PARAMS, SNPMI_STD_PARAMS(T), int num_threads, int collective,   \
+                                          int root, int parts) {                                                     \
+        return guarded([&] {                                                                                         \
+            grm_add_bed_reduce_impl<T>(SNPMI_BED_SEL, SNPMI_STD_ARGS, stats, collective, root, PARTS);               \
+        });                                                                                                          \
+    }                                                                                                                \
+    int snpmi_grm_add_packed_##SUFFIX(SNPMI_PACKED_PARAMS, SNPMI_STD_PARAMS(T)) {                                   \
+        return guarded([&] { grm_add_packed_impl<T>(SNPMI_PACKED_SNPS, SNPMI_STD_ARGS, stats); });                   \
+    }                                                                                                                \
+    int snpmi_grm_add_packed_reduce_##SUFFIX(SNPMI_PACKED_PARAMS, SNPMI_STD_PARAMS(T), int collective, int root,    \
+                                             int parts, void* syrk_done) {                                           \
+        return guarded([&] {                                                                                         \
+            grm_add_packed_reduce_impl<T>(SNPMI_PACKED_SNPS, SNPMI_STD_ARGS, stats, collective, root, PARTS,         \
+                                          (hipEvent_t)syrk_done);                                                    \
+        });                                                                                                          \
+    }                                                                                                                \
+    int snpmi_grm_add_dense_##SUFFIX(const T* val, uint64_t rows, uint64_t cols, int order_c) {                     \
+        return guarded([&] { grm_add_dense_impl<T>(val, rows, cols, order_c); });                                    \
     }
-SNPMI_GRM_ADD(f32, float, SNPMI_DT_F32)
-SNPMI_GRM_ADD(f64, double, SNPMI_DT_F64)
-
-int snpmi_grm_add_packed_f32(const uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_t n_sid, int count_a1,
-                             int std_kind, double a, double b, int use_stats, float* stats) {
-    return guarded([&] { grm_add_packed_impl<float>(packed, pitch, n_iid, n_sid, count_a1, std_kind, a, b, use_stats, stats); });
-}
-int snpmi_grm_add_packed_f64(const uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_t n_sid, int count_a1,
-                             int std_kind, double a, double b, int use_stats, double* stats) {
-    return guarded([&] { grm_add_packed_impl<double>(packed, pitch, n_iid, n_sid, count_a1, std_kind, a, b, use_stats, stats); });
-}
-
-int snpmi_grm_add_packed_reduce_f32(const uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_t n_sid,
-                                    int count_a1, int std_kind, double a, double b, int use_stats, float* stats,
-                                    int collective, int root, int parts, void* syrk_done) {
-    return guarded([&] {
-        grm_add_packed_reduce_impl<float>(packed, pitch, n_iid, n_sid, count_a1, std_kind, a, b, use_stats, stats,
-                                          collective, root, parts, (hipEvent_t)syrk_done);
-    });
-}
-
-int snpmi_grm_add_packed_reduce_f64(const uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_t n_sid,
-                                    int count_a1, int std_kind, double a, double b, int use_stats, double* stats,
-                                    int collective, int root, int parts, void* syrk_done) {
-    // parts: the CRT path's own residue chunks are the groups
-    return guarded([&] {
-        grm_add_packed_reduce_impl<double>(packed, pitch, n_iid, n_sid, count_a1, std_kind, a, b, use_stats, stats,
-                                           collective, root, std::max(parts, 1), (hipEvent_t)syrk_done);
-    });
-}
-
-int snpmi_grm_add_bed_reduce_f32(const char* path, uint64_t n_iid, uint64_t n_sid, int count_a1, const uint64_t* iid_idx,
-                                 uint64_t n_out_iid, const uint64_t* sid_idx, uint64_t n_out_sid, int std_kind,
-                                 double a, double b, int use_stats, float* stats, int num_threads, int collective,
-                                 int root, int parts) {
-    return guarded([&] {
-        grm_add_bed_reduce_impl<float>(path, n_iid, n_sid, count_a1, iid_idx, n_out_iid, sid_idx, n_out_sid, std_kind,
-                                       a, b, use_stats, stats, num_threads, collective, root, parts);
-    });
-}
-int snpmi_grm_add_bed_reduce_f64(const char* path, uint64_t n_iid, uint64_t n_sid, int count_a1, const uint64_t* iid_idx,
-                                 uint64_t n_out_iid, const uint64_t* sid_idx, uint64_t n_out_sid, int std_kind,
-                                 double a, double b, int use_stats, double* stats, int num_threads, int collective,
-                                 int root, int parts) {
-    return guarded([&] {
-        grm_add_bed_reduce_impl<double>(path, n_iid, n_sid, count_a1, iid_idx, n_out_iid, sid_idx, n_out_sid,
-                                        std_kind, a, b, use_stats, stats, num_threads, collective, root,
-                                        std::max(parts, 1));
-    });
-}
-
-int snpmi_grm_add_dense_f32(const float* val, uint64_t rows, uint64_t cols, int order_c) {
-    return guarded([&] { grm_add_dense_impl<float>(val, rows, cols, order_c); });
-}
-int snpmi_grm_add_dense_f64(const double* val, uint64_t rows, uint64_t cols, int order_c) {
-    return guarded([&] { grm_add_dense_impl<double>(val, rows, cols, order_c); });
-}
+SNPMI_GRM_ADD(f32, float, parts)
+SNPMI_GRM_ADD(f64, double, std::max(parts, 1))
 
 int snpmi_grm_session_tiles(void** tiles, uint64_t* count) {
     return guarded([&] {
         std::lock_guard<std::recursive_mutex> lk(g_call_mutex);
-        SNPMI_REQUIRE(g_session.active, SNPMI_E_ARG, "no GRM session (call snpmi_grm_begin)");
+        session_check_open();
         Device& d = device();
         void* t = session_tiles(d);
         const uint64_t cnt = n_tiles_upper(g_session.n) * kTile * kTile;
@@ -2168,7 +2244,7 @@ int snpmi_grm_session_tiles(void** tiles, uint64_t* count) {
 int snpmi_grm_session_sum(int collective, int root, int parts) {
     return guarded([&] {
         std::lock_guard<std::recursive_mutex> lk(g_call_mutex);
-        SNPMI_REQUIRE(g_session.active, SNPMI_E_ARG, "no GRM session (call snpmi_grm_begin)");
+        session_check_open();
         Device& d = device();
         const int rt = collective == 1 ? root : -1;
         g_last_groups = 1;
@@ -2185,7 +2261,7 @@ int snpmi_grm_session_sum(int collective, int root, int parts) {
 int snpmi_grm_end(int diag_k_to_n, double* factor, void* K_out) {
     return guarded([&] {
         std::lock_guard<std::recursive_mutex> lk(g_call_mutex);
-        SNPMI_REQUIRE(g_session.active, SNPMI_E_ARG, "no GRM session (call snpmi_grm_begin)");
+        session_check_open();
         Device& d = device();
         g_session.active = false;
         if (!K_out) {  // end without a result (a non-root rank after an RCCL reduce, an aborted GRM)
@@ -2258,38 +2334,17 @@ int snpmi_grm_rect_begin(uint64_t n_rows, uint64_t n_cols, int dtype) {
     });
 }
 
-int snpmi_grm_rect_add_packed_f32(const uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_t n_sid, int count_a1,
-                                  int std_kind, double a, double b, int use_stats, float* stats,
-                                  const uint64_t* row_idx, const uint64_t* col_idx) {
-    return guarded([&] {
-        rect_add_packed_impl<float>(packed, pitch, n_iid, n_sid, count_a1, std_kind, a, b, use_stats, stats, row_idx, col_idx);
-    });
-}
-int snpmi_grm_rect_add_packed_f64(const uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_t n_sid, int count_a1,
-                                  int std_kind, double a, double b, int use_stats, double* stats,
-                                  const uint64_t* row_idx, const uint64_t* col_idx) {
-    return guarded([&] {
-        rect_add_packed_impl<double>(packed, pitch, n_iid, n_sid, count_a1, std_kind, a, b, use_stats, stats, row_idx, col_idx);
-    });
-}
-int snpmi_grm_rect_add_bed_f32(const char* path, uint64_t n_iid, uint64_t n_sid, int count_a1, const uint64_t* iid_idx,
-                               uint64_t n_out_iid, const uint64_t* sid_idx, uint64_t n_out_sid, int std_kind, double a,
-                               double b, int use_stats, float* stats, int num_threads, const uint64_t* row_idx,
-                               const uint64_t* col_idx) {
-    return guarded([&] {
-        rect_add_bed_impl<float>(path, n_iid, n_sid, count_a1, iid_idx, n_out_iid, sid_idx, n_out_sid, std_kind, a, b,
-                                 use_stats, stats, num_threads, row_idx, col_idx);
-    });
-}
-int snpmi_grm_rect_add_bed_f64(const char* path, uint64_t n_iid, uint64_t n_sid, int count_a1, const uint64_t* iid_idx,
-                               uint64_t n_out_iid, const uint64_t* sid_idx, uint64_t n_out_sid, int std_kind, double a,
-                               double b, int use_stats, double* stats, int num_threads, const uint64_t* row_idx,
-                               const uint64_t* col_idx) {
-    return guarded([&] {
-        rect_add_bed_impl<double>(path, n_iid, n_sid, count_a1, iid_idx, n_out_iid, sid_idx, n_out_sid, std_kind, a, b,
-                                  use_stats, stats, num_threads, row_idx, col_idx);
-    });
-}
+#define SNPMI_GRM_RECT_ADD(SUFFIX, T)                                                                               \
+    int snpmi_grm_rect_add_packed_##SUFFIX(SNPMI_PACKED_PARAMS, SNPMI_STD_PARAMS(T), const uint64_t* row_idx,       \
+                                           const uint64_t* col_idx) {                                                \
+        return guarded([&] { rect_add_packed_impl<T>(SNPMI_PACKED_SNPS, SNPMI_STD_ARGS, stats, row_idx, col_idx); }); \
+    }                                                                                                                \
+    int snpmi_grm_rect_add_bed_##SUFFIX(SNPMI_BED_PARAMS, SNPMI_STD_PARAMS(T), int num_threads,                     \
+                                        const uint64_t* row_idx, const uint64_t* col_idx) {                         \
+        return guarded([&] { rect_add_bed_impl<T>(SNPMI_BED_SEL, SNPMI_STD_ARGS, stats, row_idx, col_idx); });       \
+    }
+SNPMI_GRM_RECT_ADD(f32, float)
+SNPMI_GRM_RECT_ADD(f64, double)
 
 int snpmi_grm_rect_end(double scale, int order_c, void* K_out) {
     return guarded([&] {
@@ -2311,67 +2366,43 @@ int snpmi_grm_rect_end(double scale, int order_c, void* K_out) {
     });
 }
 
-int snpmi_standardize_f32(float* val, uint64_t rows, uint64_t cols, int order_c, int is_beta, double a, double b,
-                          int apply_in_place, int use_stats, float* stats, int) {
-    return guarded([&] { standardize_impl<float>(val, rows, cols, order_c, is_beta, a, b, apply_in_place, use_stats, stats); });
-}
-int snpmi_standardize_f64(double* val, uint64_t rows, uint64_t cols, int order_c, int is_beta, double a, double b,
-                          int apply_in_place, int use_stats, double* stats, int) {
-    return guarded([&] { standardize_impl<double>(val, rows, cols, order_c, is_beta, a, b, apply_in_place, use_stats, stats); });
-}
-
-int snpmi_subset_f64_f64(const double* val, uint64_t rows, uint64_t cols, uint64_t k, int in_c, const uint64_t* ri,
-                         uint64_t nr, const uint64_t* ci, uint64_t nc, int out_c, double* out, int) {
-    return guarded([&] { subset_impl<double, double>(val, rows, cols, k, in_c, ri, nr, ci, nc, out_c, out); });
-}
-int snpmi_subset_f32_f64(const float* val, uint64_t rows, uint64_t cols, uint64_t k, int in_c, const uint64_t* ri,
-                         uint64_t nr, const uint64_t* ci, uint64_t nc, int out_c, double* out, int) {
-    return guarded([&] { subset_impl<float, double>(val, rows, cols, k, in_c, ri, nr, ci, nc, out_c, out); });
-}
-int snpmi_subset_f32_f32(const float* val, uint64_t rows, uint64_t cols, uint64_t k, int in_c, const uint64_t* ri,
-                         uint64_t nr, const uint64_t* ci, uint64_t nc, int out_c, float* out, int) {
-    return guarded([&] { subset_impl<float, float>(val, rows, cols, k, in_c, ri, nr, ci, nc, out_c, out); });
-}
-
-#define SNPMI_GRM_BED(SUFFIX, T)                                                                                    \
-    int snpmi_grm_bed_##SUFFIX(const char* path, uint64_t n_iid, uint64_t n_sid, int count_a1,                    \
-                               const uint64_t* iid_idx, uint64_t n_out_iid, const uint64_t* sid_idx,              \
-                               uint64_t n_out_sid, int std_kind, double a, double b, int use_stats, T* stats,     \
-                               int diag, double* factor, T* K_out, int num_threads) {                             \
-        return guarded([&] {                                                                                        \
-            grm_bed_impl<T>(path, n_iid, n_sid, count_a1, iid_idx, n_out_iid, sid_idx, n_out_sid, std_kind, a, b,  \
-                            use_stats, stats, diag, factor, K_out, num_threads);                                   \
-        });                                                                                                         \
+#define SNPMI_DENSE(SUFFIX, T)                                                                                      \
+    int snpmi_standardize_##SUFFIX(T* val, uint64_t rows, uint64_t cols, int order_c, int is_beta, double a,        \
+                                   double b, int apply_in_place, int use_stats, T* stats, int) {                    \
+        return guarded([&] {                                                                                         \
+            standardize_impl<T>(val, rows, cols, order_c, is_beta, a, b, apply_in_place, use_stats, stats);          \
+        });                                                                                                          \
+    }                                                                                                                \
+    int snpmi_grm_bed_##SUFFIX(SNPMI_BED_PARAMS, SNPMI_STD_PARAMS(T), int diag, double* factor, T* K_out,           \
+                               int num_threads) {                                                                    \
+        return guarded([&] { grm_bed_impl<T>(SNPMI_BED_SEL, SNPMI_STD_ARGS, stats, diag, factor, K_out); });         \
+    }                                                                                                                \
+    int snpmi_grm_dense_##SUFFIX(const T* val, uint64_t rows, uint64_t cols, int order_c, SNPMI_STD_PARAMS(T),      \
+                                 int diag, double* factor, T* K_out) {                                               \
+        return guarded([&] {                                                                                         \
+            grm_dense_impl<T>(val, rows, cols, order_c, SNPMI_STD_ARGS, stats, diag, factor, K_out);                 \
+        });                                                                                                          \
+    }                                                                                                                \
+    int snpmi_diag_k_to_n_snps_##SUFFIX(T* val, uint64_t rows, uint64_t cols, double* factor) {                     \
+        return guarded([&] { snp_scale_impl<T>(val, rows * cols, (double)rows, 0, 1.0, factor); });                  \
+    }                                                                                                                \
+    int snpmi_scale_##SUFFIX(T* val, uint64_t count, double scale) {                                                \
+        return guarded([&] { snp_scale_impl<T>(val, count, 0.0, 1, scale, nullptr); });                              \
+    }                                                                                                                \
+    int snpmi_diag_k_to_n_##SUFFIX(T* K, uint64_t n, double* factor) {                                              \
+        return guarded([&] { diag_k_to_n_impl<T>(K, n, factor); });                                                  \
     }
-SNPMI_GRM_BED(f32, float)
-SNPMI_GRM_BED(f64, double)
+SNPMI_DENSE(f32, float)
+SNPMI_DENSE(f64, double)
 
-int snpmi_grm_dense_f32(const float* val, uint64_t rows, uint64_t cols, int order_c, int std_kind, double a, double b,
-                        int use_stats, float* stats, int diag, double* factor, float* K_out) {
-    return guarded([&] { grm_dense_impl<float>(val, rows, cols, order_c, std_kind, a, b, use_stats, stats, diag, factor, K_out); });
-}
-int snpmi_grm_dense_f64(const double* val, uint64_t rows, uint64_t cols, int order_c, int std_kind, double a,
-                        double b, int use_stats, double* stats, int diag, double* factor, double* K_out) {
-    return guarded([&] { grm_dense_impl<double>(val, rows, cols, order_c, std_kind, a, b, use_stats, stats, diag, factor, K_out); });
-}
-int snpmi_diag_k_to_n_snps_f32(float* val, uint64_t rows, uint64_t cols, double* factor) {
-    return guarded([&] { snp_scale_impl<float>(val, rows * cols, (double)rows, 0, 1.0, factor); });
-}
-int snpmi_diag_k_to_n_snps_f64(double* val, uint64_t rows, uint64_t cols, double* factor) {
-    return guarded([&] { snp_scale_impl<double>(val, rows * cols, (double)rows, 0, 1.0, factor); });
-}
-int snpmi_scale_f32(float* val, uint64_t count, double scale) {
-    return guarded([&] { snp_scale_impl<float>(val, count, 0.0, 1, scale, nullptr); });
-}
-int snpmi_scale_f64(double* val, uint64_t count, double scale) {
-    return guarded([&] { snp_scale_impl<double>(val, count, 0.0, 1, scale, nullptr); });
-}
-int snpmi_diag_k_to_n_f32(float* K, uint64_t n, double* factor) {
-    return guarded([&] { diag_k_to_n_impl<float>(K, n, factor); });
-}
-int snpmi_diag_k_to_n_f64(double* K, uint64_t n, double* factor) {
-    return guarded([&] { diag_k_to_n_impl<double>(K, n, factor); });
-}
+#define SNPMI_SUBSET(SUFFIX, S, D)                                                                                  \
+    int snpmi_subset_##SUFFIX(const S* val, uint64_t rows, uint64_t cols, uint64_t k, int in_c, const uint64_t* ri, \
+                              uint64_t nr, const uint64_t* ci, uint64_t nc, int out_c, D* out, int) {               \
+        return guarded([&] { subset_impl<S, D>(val, rows, cols, k, in_c, ri, nr, ci, nc, out_c, out); });            \
+    }
+SNPMI_SUBSET(f64_f64, double, double)
+SNPMI_SUBSET(f32_f64, float, double)
+SNPMI_SUBSET(f32_f32, float, float)
 
 // ---------------------------------------------------------------------- device-resident API
 uint64_t snpmi_packed_pitch(uint64_t n_iid) { return packed_pitch(n_iid); }
@@ -2458,6 +2489,16 @@ int snpmi_set_stream(int which) {
     return guarded([&] {
         SNPMI_REQUIRE(which == 0 || which == 2, SNPMI_E_ARG, "stream must be 0 (compute) or 2 (aux)");
         g_sel_stream = which;
+    });
+}
+
+int snpmi_device_memory(uint64_t* free_bytes, uint64_t* total_bytes) {
+    return guarded([&] {
+        device();
+        size_t f = 0, t = 0;
+        SNPMI_HIP(hipMemGetInfo(&f, &t));
+        if (free_bytes) *free_bytes = f;
+        if (total_bytes) *total_bytes = t;
     });
 }
 
@@ -2663,15 +2704,15 @@ int snpmi_bed_gather_packed(const char* path, uint64_t n_iid, uint64_t n_sid, co
 int snpmi_dev_snp_stats(const uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_t n_sid, int count_a1,
                         int std_kind, double a, double b, int use_stats, int dtype, void* stats, void* lut) {
     return guarded([&] {
-        SNPMI_REQUIRE(pitch % 64 == 0 && pitch >= ceil_div(n_iid, 4), SNPMI_E_ARG, "pitch must be snpmi_packed_pitch");
-        launch_snp_stats(packed, pitch, n_iid, n_sid, count_a1, std_kind, a, b, use_stats, dtype, stats, lut, stream());
+        check_pitch(pitch, n_iid);
+        launch_snp_stats(packed, pitch, n_iid, n_sid, count_a1, SNPMI_STD_ARGS, dtype, stats, lut, stream());
     });
 }
 
 int snpmi_dev_decode(const uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_t n_sid, const void* lut,
                      int dtype, int order_c, void* out, uint64_t ld) {
     return guarded([&] {
-        SNPMI_REQUIRE(pitch % 64 == 0 && pitch >= ceil_div(n_iid, 4), SNPMI_E_ARG, "pitch must be snpmi_packed_pitch");
+        check_pitch(pitch, n_iid);
         if (!order_c) SNPMI_REQUIRE(ld % 16 == 0 && ld >= n_iid, SNPMI_E_ARG, "F-order ld must be >= n_iid, % 16");
         else SNPMI_REQUIRE(ld >= n_sid, SNPMI_E_ARG, "C-order ld must be >= n_sid");
         launch_decode(packed, pitch, n_iid, n_sid, lut, dtype, order_c, out, ld, stream());
@@ -2683,10 +2724,9 @@ int snpmi_dev_decode_standardize(const uint8_t* packed, uint64_t pitch, uint64_t
                                  void* stats, void* lut, void* out, uint64_t ld) {
     return guarded([&] {
         SNPMI_REQUIRE(dtype == SNPMI_DT_F32, SNPMI_E_ARG, "fused decode+standardize is f32 only");
-        SNPMI_REQUIRE(pitch % 64 == 0 && pitch >= ceil_div(n_iid, 4), SNPMI_E_ARG, "pitch must be snpmi_packed_pitch");
+        check_pitch(pitch, n_iid);
         SNPMI_REQUIRE(ld % 16 == 0 && ld >= n_iid, SNPMI_E_ARG, "F-order ld must be >= n_iid, % 16");
-        launch_decode_std_fused(packed, pitch, n_iid, n_sid, count_a1, std_kind, a, b, use_stats, stats, lut, out, ld,
-                                stream());
+        launch_decode_std_fused(packed, pitch, n_iid, n_sid, count_a1, SNPMI_STD_ARGS, stats, lut, out, ld, stream());
     });
 }
 
@@ -2694,7 +2734,7 @@ int snpmi_dev_repack(const uint8_t* src, uint64_t src_pitch, uint64_t n_src, con
                      uint64_t n_sid, uint8_t* dst, uint64_t dst_pitch) {
     return guarded([&] {
         std::lock_guard<std::recursive_mutex> lk(g_call_mutex);  // shared scratch slots
-        SNPMI_REQUIRE(dst_pitch % 64 == 0 && dst_pitch >= ceil_div(n_out, 4), SNPMI_E_ARG, "bad dst pitch");
+        check_pitch(dst_pitch, n_out, "bad dst pitch");
         Device& d = device();
         uint32_t* plan = (uint32_t*)d.get(Device::S_IDX32, repack_plan_entries(n_out) * 4);
         uint32_t* win = (uint32_t*)d.get(Device::S_WIN, repack_win_entries(n_out) * 4);
@@ -2708,216 +2748,8 @@ int snpmi_dev_syrk_packed(const uint8_t* packed, uint64_t pitch, uint64_t n_iid,
     return guarded([&] {
         std::lock_guard<std::recursive_mutex> lk(g_call_mutex);  // shared scratch slots
         SNPMI_REQUIRE(dtype == SNPMI_DT_F32 || dtype == SNPMI_DT_F64, SNPMI_E_ARG, "GRM dtype must be f32/f64");
-        SNPMI_REQUIRE(pitch % 64 == 0 && pitch >= ceil_div(n_iid, 4), SNPMI_E_ARG, "pitch must be snpmi_packed_pitch");
+        check_pitch(pitch, n_iid);
         syrk_packed_auto(device(), packed, pitch, n_iid, n_sid, lut, dtype, whole_dest(K_tiles, n_iid), accumulate);
-    });
-}
-
-uint64_t snpmi_grm_part_blocks(uint64_t n_iid, int part_rank, int part_world) {
-    if (part_world < 1 || part_rank < 0 || part_rank >= part_world) return 0;
-    return grm_part_blocks(n_iid, part_rank, part_world);
-}
-
-// host copy of the last part layout asked for (snpmi_grm_part_coords is called per block)
-static std::mutex g_layout_mutex;
-static std::vector<uint32_t> g_layout;
-static uint64_t g_layout_key[3] = {~0ull, 0, 0};
-static const std::vector<uint32_t>& host_layout(uint64_t nb, int rank, int world) {
-    if (g_layout_key[0] != nb || g_layout_key[1] != (uint64_t)rank || g_layout_key[2] != (uint64_t)world) {
-        part_layout(nb, rank, world, g_layout);
-        g_layout_key[0] = nb;
-        g_layout_key[1] = (uint64_t)rank;
-        g_layout_key[2] = (uint64_t)world;
-    }
-    return g_layout;
-}
-
-int snpmi_grm_part_coords(uint64_t n_iid, int part_rank, int part_world, uint64_t local_block, uint64_t* row0,
-                          uint64_t* col0) {
-    return guarded([&] {
-        SNPMI_REQUIRE(part_world >= 1 && part_rank >= 0 && part_rank < part_world, SNPMI_E_ARG, "bad partition");
-        std::lock_guard<std::mutex> lk(g_layout_mutex);
-        const auto& tab = host_layout(ceil_div(n_iid, 256), part_rank, part_world);
-        SNPMI_REQUIRE(local_block < tab.size(), SNPMI_E_INDEX, "block out of range");
-        if (row0) *row0 = (uint64_t)(tab[local_block] & 0xffffu) * 256;
-        if (col0) *col0 = (uint64_t)(tab[local_block] >> 16) * 256;
-    });
-}
-
-int snpmi_grm_part_coords_all(uint64_t n_iid, int part_rank, int part_world, uint64_t* coords) {
-    return guarded([&] {
-        SNPMI_REQUIRE(part_world >= 1 && part_rank >= 0 && part_rank < part_world, SNPMI_E_ARG, "bad partition");
-        std::lock_guard<std::mutex> lk(g_layout_mutex);
-        const auto& tab = host_layout(ceil_div(n_iid, 256), part_rank, part_world);
-        SNPMI_REQUIRE(coords != nullptr || tab.empty(), SNPMI_E_ARG, "coords is NULL");
-        for (uint64_t w = 0; w < tab.size(); w++) {
-            coords[2 * w] = (uint64_t)(tab[w] & 0xffffu) * 256;
-            coords[2 * w + 1] = (uint64_t)(tab[w] >> 16) * 256;
-        }
-    });
-}
-
-// cfg5 from a file (K too large to replicate): rank part_rank of part_world streams EVERY SNP of
-// the .bed (stats need all iids of a SNP; each rank computes them itself -- no exchange) and
-// accumulates only its own 256x256 K blocks (snpmi_grm_part_coords) in HBM, then copies them to
-// blocks_out (n_local x 65536 f32, row-major blocks; may be a memory-mapped file).
-}  // extern "C"
-
-namespace snpmi {
-template <typename T>
-static void grm_part_bed_impl(const char* path, uint64_t n_iid, uint64_t n_sid, int count_a1, const uint64_t* iid_idx,
-                              uint64_t n_out_iid, const uint64_t* sid_idx, uint64_t n_out_sid, int std_kind, double a,
-                              double b, int use_stats, T* stats, int part_rank, int part_world, T* blocks_out,
-                              int num_threads) {
-    std::lock_guard<std::recursive_mutex> lk(g_call_mutex);
-    SNPMI_REQUIRE(part_world >= 1 && part_rank >= 0 && part_rank < part_world, SNPMI_E_ARG, "bad rank / world");
-    const uint64_t n_out = iid_idx ? n_out_iid : n_iid;
-    const uint64_t nloc = grm_part_blocks(n_out, part_rank, part_world);
-    SNPMI_REQUIRE(blocks_out != nullptr || nloc == 0, SNPMI_E_ARG, "blocks_out is NULL");
-    Device& d = device();
-    const uint64_t bytes = std::max<uint64_t>(nloc, 1) * 256 * 256 * sizeof(T);
-    // blocks_out in device memory: the SYRK accumulates into it directly (K stays in HBM, no
-    // scratch, no copy-out); host memory: scratch tiles + a pinned-bounce copy at the end
-    const bool dev_out = nloc && is_device_ptr(d, blocks_out);
-    T* blocks = dev_out ? blocks_out : (T*)d.get(Device::S_TILES, bytes);
-    const bool wrote = grm_stream_bed<T>(
-        d, true, path, n_iid, n_sid, count_a1, iid_idx, n_out_iid, sid_idx, n_out_sid, std_kind, a, b, use_stats,
-        stats, num_threads,
-        [&](const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t cnt, const T* lut, bool acc) {
-            syrk_packed_auto(d, packed, pitch, n, cnt, lut, DT<T>::v, part_dest(blocks, n, part_rank, part_world), acc);
-        });
-    if (!wrote) SNPMI_HIP(hipMemsetAsync(blocks, 0, dev_out ? nloc * 256 * 256 * sizeof(T) : bytes, d.stream));
-    const size_t bb = 256 * 256 * sizeof(T);  // one block per "row" of the pinned-bounce copy
-    if (nloc && !dev_out) d2h_rows(d, blocks_out, bb, blocks, bb, bb, nloc, resolve_threads(num_threads));
-    SNPMI_HIP(hipStreamSynchronize(d.stream));
-}
-}  // namespace snpmi
-
-extern "C" {
-
-// cfg5 from a file (K too large to replicate): rank part_rank of part_world streams EVERY SNP of
-// the .bed (stats need all iids of a SNP; each rank computes them itself -- no exchange) and
-// accumulates only its own 256x256 K blocks (snpmi_grm_part_coords) in HBM, then copies them to
-// blocks_out (n_local x 65536 values, row-major blocks; may be a memory-mapped file).
-int snpmi_grm_part_bed_f32(const char* path, uint64_t n_iid, uint64_t n_sid, int count_a1, const uint64_t* iid_idx,
-                           uint64_t n_out_iid, const uint64_t* sid_idx, uint64_t n_out_sid, int std_kind, double a,
-                           double b, int use_stats, float* stats, int part_rank, int part_world, float* blocks_out,
-                           int num_threads) {
-    return guarded([&] {
-        grm_part_bed_impl<float>(path, n_iid, n_sid, count_a1, iid_idx, n_out_iid, sid_idx, n_out_sid, std_kind, a, b,
-                                 use_stats, stats, part_rank, part_world, blocks_out, num_threads);
-    });
-}
-int snpmi_grm_part_bed_f64(const char* path, uint64_t n_iid, uint64_t n_sid, int count_a1, const uint64_t* iid_idx,
-                           uint64_t n_out_iid, const uint64_t* sid_idx, uint64_t n_out_sid, int std_kind, double a,
-                           double b, int use_stats, double* stats, int part_rank, int part_world, double* blocks_out,
-                           int num_threads) {
-    return guarded([&] {
-        grm_part_bed_impl<double>(path, n_iid, n_sid, count_a1, iid_idx, n_out_iid, sid_idx, n_out_sid, std_kind, a,
-                                  b, use_stats, stats, part_rank, part_world, blocks_out, num_threads);
-    });
-}
-
-int snpmi_dev_syrk_packed_part(const uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_t n_sid, const void* lut,
-                               int part_rank, int part_world, void* blocks, int accumulate) {
-    return guarded([&] {
-        std::lock_guard<std::recursive_mutex> lk(g_call_mutex);  // shared scratch slots
-        SNPMI_REQUIRE(part_world >= 1 && part_rank >= 0 && part_rank < part_world, SNPMI_E_ARG, "bad partition");
-        SNPMI_REQUIRE(pitch % 64 == 0 && pitch >= ceil_div(n_iid, 4), SNPMI_E_ARG, "pitch must be snpmi_packed_pitch");
-        syrk_packed_auto(device(), packed, pitch, n_iid, n_sid, lut, SNPMI_DT_F32,
-                         part_dest(blocks, n_iid, part_rank, part_world), accumulate);
-    });
-}
-
-}  // extern "C"
-
-namespace snpmi {
-// K[ri, ci] restricted to part `part_rank`'s blocks (the rest 0): the parts' outputs summed over
-// the ranks are the sub-matrix (snpmi_grm_part_extract_*, the PartitionedKernel reader)
-template <typename T>
-static void part_extract_impl(const T* blocks, uint64_t n, int part_rank, int part_world, const uint64_t* ri,
-                              uint64_t nr, const uint64_t* ci, uint64_t nc, int order_c, double scale, T* out) {
-    std::lock_guard<std::recursive_mutex> lk(g_call_mutex);
-    SNPMI_REQUIRE(part_world >= 1 && part_rank >= 0 && part_rank < part_world, SNPMI_E_ARG, "bad partition");
-    SNPMI_REQUIRE(out != nullptr || nr * nc == 0, SNPMI_E_ARG, "out is NULL");
-    Device& d = device();
-    const uint64_t nloc = grm_part_blocks(n, part_rank, part_world);
-    SNPMI_REQUIRE(nloc == 0 || (blocks && is_device_ptr(d, blocks)), SNPMI_E_ARG,
-                  "blocks must be device memory of the current device");
-    for (uint64_t k = 0; ri && k < nr; k++) SNPMI_REQUIRE(ri[k] < n, SNPMI_E_INDEX, "iid0 index out of range");
-    for (uint64_t k = 0; ci && k < nc; k++) SNPMI_REQUIRE(ci[k] < n, SNPMI_E_INDEX, "iid1 index out of range");
-    SNPMI_REQUIRE(ri || nr <= n, SNPMI_E_INDEX, "iid0 count exceeds n");
-    SNPMI_REQUIRE(ci || nc <= n, SNPMI_E_INDEX, "iid1 count exceeds n");
-    if (nr * nc == 0) return;
-    const PartTables pt = part_tables(ceil_div(n, 256), part_rank, part_world);
-    uint64_t* dri = nullptr;
-    uint64_t* dci = nullptr;
-    if (ri) {
-        dri = (uint64_t*)d.get(Device::S_IDX, nr * 8);
-        SNPMI_HIP(hipMemcpyAsync(dri, ri, nr * 8, hipMemcpyHostToDevice, d.stream));
-    }
-    if (ci) {
-        dci = (uint64_t*)d.get(Device::S_IDX2, nc * 8);
-        SNPMI_HIP(hipMemcpyAsync(dci, ci, nc * 8, hipMemcpyHostToDevice, d.stream));
-    }
-    const bool dev = is_device_ptr(d, out);
-    T* o = dev ? out : (T*)d.get(Device::S_K, nr * nc * sizeof(T));
-    launch_part_extract(blocks, pt.lslot, DT<T>::v, dri, nr, dci, nc, order_c, scale, o, d.stream);
-    if (!dev) SNPMI_HIP(hipMemcpyAsync(out, o, nr * nc * sizeof(T), hipMemcpyDeviceToHost, d.stream));
-    SNPMI_HIP(hipStreamSynchronize(d.stream));
-}
-
-template <typename T>
-static void part_trace_impl(const T* blocks, uint64_t n, int part_rank, int part_world, double* trace) {
-    std::lock_guard<std::recursive_mutex> lk(g_call_mutex);
-    SNPMI_REQUIRE(part_world >= 1 && part_rank >= 0 && part_rank < part_world, SNPMI_E_ARG, "bad partition");
-    SNPMI_REQUIRE(trace != nullptr, SNPMI_E_ARG, "trace is NULL");
-    Device& d = device();
-    *trace = 0.0;
-    if (n == 0 || grm_part_blocks(n, part_rank, part_world) == 0) return;
-    SNPMI_REQUIRE(blocks && is_device_ptr(d, blocks), SNPMI_E_ARG, "blocks must be device memory of the current device");
-    const PartTables pt = part_tables(ceil_div(n, 256), part_rank, part_world);
-    double* tr = (double*)d.get(Device::S_RED, 64);
-    launch_part_trace(blocks, pt.dslot, n, DT<T>::v, tr, d.stream);
-    SNPMI_HIP(hipMemcpyAsync(trace, tr, 8, hipMemcpyDeviceToHost, d.stream));
-    SNPMI_HIP(hipStreamSynchronize(d.stream));
-}
-}  // namespace snpmi
-
-extern "C" {
-
-int snpmi_grm_part_extract_f32(const float* blocks, uint64_t n_iid, int part_rank, int part_world, const uint64_t* ri,
-                               uint64_t nr, const uint64_t* ci, uint64_t nc, int order_c, double scale, float* out) {
-    return guarded([&] { part_extract_impl<float>(blocks, n_iid, part_rank, part_world, ri, nr, ci, nc, order_c, scale, out); });
-}
-int snpmi_grm_part_extract_f64(const double* blocks, uint64_t n_iid, int part_rank, int part_world, const uint64_t* ri,
-                               uint64_t nr, const uint64_t* ci, uint64_t nc, int order_c, double scale, double* out) {
-    return guarded([&] { part_extract_impl<double>(blocks, n_iid, part_rank, part_world, ri, nr, ci, nc, order_c, scale, out); });
-}
-int snpmi_grm_part_trace_f32(const float* blocks, uint64_t n_iid, int part_rank, int part_world, double* trace) {
-    return guarded([&] { part_trace_impl<float>(blocks, n_iid, part_rank, part_world, trace); });
-}
-int snpmi_grm_part_trace_f64(const double* blocks, uint64_t n_iid, int part_rank, int part_world, double* trace) {
-    return guarded([&] { part_trace_impl<double>(blocks, n_iid, part_rank, part_world, trace); });
-}
-int snpmi_device_memory(uint64_t* free_bytes, uint64_t* total_bytes) {
-    return guarded([&] {
-        device();
-        size_t f = 0, t = 0;
-        SNPMI_HIP(hipMemGetInfo(&f, &t));
-        if (free_bytes) *free_bytes = f;
-        if (total_bytes) *total_bytes = t;
-    });
-}
-
-int snpmi_dev_syrk_packed_part_f64(const uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_t n_sid,
-                                   const double* lut, int part_rank, int part_world, double* blocks, int accumulate) {
-    return guarded([&] {
-        std::lock_guard<std::recursive_mutex> lk(g_call_mutex);  // shared scratch slots
-        SNPMI_REQUIRE(part_world >= 1 && part_rank >= 0 && part_rank < part_world, SNPMI_E_ARG, "bad partition");
-        SNPMI_REQUIRE(pitch % 64 == 0 && pitch >= ceil_div(n_iid, 4), SNPMI_E_ARG, "pitch must be snpmi_packed_pitch");
-        syrk_packed_auto(device(), packed, pitch, n_iid, n_sid, lut, SNPMI_DT_F64,
-                         part_dest(blocks, n_iid, part_rank, part_world), accumulate);
     });
 }
 
@@ -2976,6 +2808,71 @@ int snpmi_dev_grm_trace(const void* K_tiles, uint64_t n_iid, int dtype, double* 
         launch_grm_trace(K_tiles, n_iid, dtype, tr, d.stream);
         SNPMI_HIP(hipMemcpyAsync(trace, tr, 8, hipMemcpyDeviceToHost, d.stream));
         SNPMI_HIP(hipStreamSynchronize(d.stream));
+    });
+}
+
+// ---- partitioned GRM (cfg5: each rank holds its own 256x256 blocks of K)
+uint64_t snpmi_grm_part_blocks(uint64_t n_iid, int part_rank, int part_world) {
+    return part_ok(part_rank, part_world) ? grm_part_blocks(n_iid, part_rank, part_world) : 0;
+}
+
+int snpmi_grm_part_coords(uint64_t n_iid, int part_rank, int part_world, uint64_t local_block, uint64_t* row0,
+                          uint64_t* col0) {
+    return guarded([&] {
+        check_part(part_rank, part_world);
+        std::lock_guard<std::mutex> lk(g_layout_mutex);
+        const auto& tab = host_layout(ceil_div(n_iid, 256), part_rank, part_world);
+        SNPMI_REQUIRE(local_block < tab.size(), SNPMI_E_INDEX, "block out of range");
+        if (row0) *row0 = (uint64_t)(tab[local_block] & 0xffffu) * 256;
+        if (col0) *col0 = (uint64_t)(tab[local_block] >> 16) * 256;
+    });
+}
+
+int snpmi_grm_part_coords_all(uint64_t n_iid, int part_rank, int part_world, uint64_t* coords) {
+    return guarded([&] {
+        check_part(part_rank, part_world);
+        std::lock_guard<std::mutex> lk(g_layout_mutex);
+        const auto& tab = host_layout(ceil_div(n_iid, 256), part_rank, part_world);
+        SNPMI_REQUIRE(coords != nullptr || tab.empty(), SNPMI_E_ARG, "coords is NULL");
+        for (uint64_t w = 0; w < tab.size(); w++) {
+            coords[2 * w] = (uint64_t)(tab[w] & 0xffffu) * 256;
+            coords[2 * w + 1] = (uint64_t)(tab[w] >> 16) * 256;
+        }
+    });
+}
+
+#define SNPMI_GRM_PART(SUFFIX, T)                                                                                   \
+    int snpmi_grm_part_bed_##SUFFIX(SNPMI_BED_PARAMS, SNPMI_STD_PARAMS(T), int part_rank, int part_world,           \
+                                    T* blocks_out, int num_threads) {                                                \
+        return guarded([&] {                                                                                         \
+            grm_part_bed_impl<T>(SNPMI_BED_SEL, SNPMI_STD_ARGS, stats, part_rank, part_world, blocks_out);           \
+        });                                                                                                          \
+    }                                                                                                                \
+    int snpmi_grm_part_extract_##SUFFIX(const T* blocks, uint64_t n_iid, int part_rank, int part_world,             \
+                                        const uint64_t* ri, uint64_t nr, const uint64_t* ci, uint64_t nc,           \
+                                        int order_c, double scale, T* out) {                                         \
+        return guarded([&] {                                                                                         \
+            part_extract_impl<T>(blocks, n_iid, part_rank, part_world, ri, nr, ci, nc, order_c, scale, out);         \
+        });                                                                                                          \
+    }                                                                                                                \
+    int snpmi_grm_part_trace_##SUFFIX(const T* blocks, uint64_t n_iid, int part_rank, int part_world,               \
+                                      double* trace) {                                                               \
+        return guarded([&] { part_trace_impl<T>(blocks, n_iid, part_rank, part_world, trace); });                    \
+    }
+SNPMI_GRM_PART(f32, float)
+SNPMI_GRM_PART(f64, double)
+
+// (the pair differs in its pointer types: the f32 form predates the typed one)
+int snpmi_dev_syrk_packed_part(const uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_t n_sid, const void* lut,
+                               int part_rank, int part_world, void* blocks, int accumulate) {
+    return guarded([&] {
+        dev_syrk_packed_part(SNPMI_DT_F32, packed, pitch, n_iid, n_sid, lut, part_rank, part_world, blocks, accumulate);
+    });
+}
+int snpmi_dev_syrk_packed_part_f64(const uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_t n_sid,
+                                   const double* lut, int part_rank, int part_world, double* blocks, int accumulate) {
+    return guarded([&] {
+        dev_syrk_packed_part(SNPMI_DT_F64, packed, pitch, n_iid, n_sid, lut, part_rank, part_world, blocks, accumulate);
     });
 }
 

@@ -418,13 +418,13 @@ void snp_to_dist_impl(const T* val, uint64_t rows, uint64_t cols, int order_c, d
 
 template <typename T>
 void grm_add_dist_impl(const T* dist, uint64_t rows, uint64_t cols_total, uint64_t col0, uint64_t cols, int order_c,
-                       double max_weight, int std_kind, double a, double b, int use_stats, T* stats) {
+                       double max_weight, const StdArgs& sa, T* stats) {
     std::lock_guard<std::recursive_mutex> lk(call_mutex());
     check_range(dist, rows, cols_total, col0, cols);
     uint64_t ldz = 0;
     T* Z = (T*)grm_session_operand(DT<T>::v, rows, cols, &ldz);
     if (rows == 0 || cols == 0) return;
-    SNPMI_REQUIRE(std_kind == SNPMI_STD_NONE || stats != nullptr, SNPMI_E_ARG, "stats is NULL");
+    SNPMI_REQUIRE(sa.kind == SNPMI_STD_NONE || stats != nullptr, SNPMI_E_ARG, "stats is NULL");
     Device& d = device();
     const bool dev_in = is_device_ptr(d, dist);
     const Weights<T> w = weights_of<T>(max_weight);
@@ -435,7 +435,7 @@ void grm_add_dist_impl(const T* dist, uint64_t rows, uint64_t cols_total, uint64
         const DistSrc<T> src = dist_view(d, dist, dev_in, rows, cols_total, col0 + c0, cc, order_c);
         launch_dist_to_snp(src, order_c, rows, cc, w, Z + c0 * ldz, 1, ldz, 0, d.stream);
     }
-    grm_session_add_operand(DT<T>::v, Z, ldz, cols, std_kind, a, b, use_stats, stats);
+    grm_session_add_operand(DT<T>::v, Z, ldz, cols, sa, stats);
 }
 
 }  // namespace
@@ -460,19 +460,16 @@ int snpmi_snp_to_dist_f64(const double* val, uint64_t rows, uint64_t cols, int o
                           double* out) {
     return guarded([&] { snp_to_dist_impl(val, rows, cols, order_c, max_weight, out); });
 }
-int snpmi_grm_add_dist_f32(const float* dist, uint64_t rows, uint64_t cols_total, uint64_t col0, uint64_t cols,
-                           int order_c, double max_weight, int std_kind, double a, double b, int use_stats,
-                           float* stats) {
-    return guarded([&] {
-        grm_add_dist_impl(dist, rows, cols_total, col0, cols, order_c, max_weight, std_kind, a, b, use_stats, stats);
-    });
-}
-int snpmi_grm_add_dist_f64(const double* dist, uint64_t rows, uint64_t cols_total, uint64_t col0, uint64_t cols,
-                           int order_c, double max_weight, int std_kind, double a, double b, int use_stats,
-                           double* stats) {
-    return guarded([&] {
-        grm_add_dist_impl(dist, rows, cols_total, col0, cols, order_c, max_weight, std_kind, a, b, use_stats, stats);
-    });
-}
+#define SNPMI_GRM_ADD_DIST(SUFFIX, T)                                                                               \
+    int snpmi_grm_add_dist_##SUFFIX(const T* dist, uint64_t rows, uint64_t cols_total, uint64_t col0, uint64_t cols, \
+                                    int order_c, double max_weight, int std_kind, double a, double b, int use_stats, \
+                                    T* stats) {                                                                      \
+        return guarded([&] {                                                                                         \
+            grm_add_dist_impl(dist, rows, cols_total, col0, cols, order_c, max_weight,                               \
+                              StdArgs{std_kind, a, b, use_stats}, stats);                                            \
+        });                                                                                                          \
+    }
+SNPMI_GRM_ADD_DIST(f32, float)
+SNPMI_GRM_ADD_DIST(f64, double)
 
 }  // extern "C"

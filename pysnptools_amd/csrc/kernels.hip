@@ -1992,9 +1992,11 @@ int g_variant_extract = 0;
 
 #define SNPMI_LAUNCH_CHECK() SNPMI_HIP(hipGetLastError())
 
-void launch_snp_stats(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, int count_a1, int std_kind,
-                      double a, double b, int use_stats, int dtype, void* stats, void* lut, hipStream_t st) {
+void launch_snp_stats(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, int count_a1, const StdArgs& sa,
+                      int dtype, void* stats, void* lut, hipStream_t st) {
     if (m == 0) return;
+    const int std_kind = sa.kind, use_stats = sa.use_stats;
+    const double a = sa.a, b = sa.b;
     // 4 waves per SNP once a column is >= 16 KiB (tools/ubench.py / bench A/B: decode variant 6
     // forces one wave per SNP)
     const bool wide = n >= 65536 && g_variant_decode != 6;
@@ -2072,9 +2074,10 @@ void launch_decode(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m
 }
 
 void launch_decode_std_fused(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, int count_a1,
-                             int std_kind, double a, double b, int use_stats, void* stats, void* lut, void* out,
-                             uint64_t ld, hipStream_t st) {
+                             const StdArgs& sa, void* stats, void* lut, void* out, uint64_t ld, hipStream_t st) {
     if (m == 0 || n == 0) return;
+    const int std_kind = sa.kind, use_stats = sa.use_stats;
+    const double a = sa.a, b = sa.b;
     const uint64_t col_bytes = ceil_div(n, 64) * 16;
     if (g_variant_decode != 1 && col_bytes <= kLdsColMax) {
         SNPMI_HIP(hipFuncSetAttribute((const void*)k_decode_std_lds_f32, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -2243,7 +2246,9 @@ void launch_dense_codes(const float* Z, uint64_t ldz, uint64_t n, uint64_t m, ui
 }
 
 void launch_dense_standardize(void* val, uint64_t rows, uint64_t cols, uint64_t ld, int order_c, int dtype,
-                              int std_kind, double a, double b, int use_stats, void* stats, hipStream_t st) {
+                              const StdArgs& sa, void* stats, hipStream_t st) {
+    const int std_kind = sa.kind, use_stats = sa.use_stats;
+    const double a = sa.a, b = sa.b;
     if (cols == 0 || std_kind == SNPMI_STD_NONE) return;
     const size_t es = dtype == SNPMI_DT_F32 ? 4 : 8;
     if (!order_c) {

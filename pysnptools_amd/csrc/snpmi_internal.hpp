@@ -127,6 +127,29 @@ hipStream_t stream();  // the calling thread's current stream (compute, or aux a
 void* pinned(int slot, size_t bytes);
 void release_pinned();
 
+// ------------------------------------------------------------------ argument blocks
+// What the C ABI spells as loose scalars travels below it as three plain blocks (api.hip builds
+// them at the ABI boundary).
+// The standardizer of one call.  The stats array is not part of it: each layer passes its own (the
+// caller's host array, the device copy, or a per-chunk offset into either).
+struct StdArgs {
+    int kind;       // SNPMI_STD_*
+    double a, b;    // Beta's shape
+    int use_stats;  // 1: the stats are given (a trained standardizer), 0: computed and written
+};
+// A selection of a .bed file: the file's own counts, the index lists (NULL = all, in file order)
+// and the resolved counts of the selection (api.hip bed_sel is the only place that resolves them).
+struct BedSel {
+    const char* path;
+    uint64_t n_iid, n_sid;
+    int count_a1;
+    const uint64_t* iid_idx;
+    const uint64_t* sid_idx;
+    int num_threads;
+    uint64_t n_out, m_out;  // iids / SNPs selected
+};
+// Packed SNP columns in HBM: codes [m][pitch] of n iids (PackedSnps, after PackedSide below)
+
 // ------------------------------------------------------------------ api.hip services for dist.hip
 // one API call at a time per process (scratch slots and the stream are shared): every entry point
 // that touches them holds this lock
@@ -135,11 +158,10 @@ std::recursive_mutex& call_mutex();
 bool is_device_ptr(Device& d, const void* p);
 // The open GRM session's F-order dense operand buffer for `cols` SNPs of its n iids (checks the
 // session, dtype and n; *ldz = round_up(n, 256), which meets snpmi_dev_syrk_dense's contract), and
-// the add of a block written there: in-place standardize (host stats [cols][2], read if use_stats,
+// the add of a block written there: in-place standardize (host stats [cols][2], read if sa.use_stats,
 // else written), Z Z^T into the session's tiles, session marked written.  Callers hold call_mutex.
 void* grm_session_operand(int dtype, uint64_t rows, uint64_t cols, uint64_t* ldz);
-void grm_session_add_operand(int dtype, void* Z, uint64_t ldz, uint64_t cols, int std_kind, double a, double b,
-                             int use_stats, void* stats);
+void grm_session_add_operand(int dtype, void* Z, uint64_t ldz, uint64_t cols, const StdArgs& sa, void* stats);
 
 // ------------------------------------------------------------------ kernel launchers (kernels.hip)
 // The tuning / test hooks of snpmi_set_kernel_variant live beside the code that reads them; api.hip's
@@ -180,13 +202,11 @@ struct PartTables {
 };
 PartTables part_tables(uint64_t nb, int rank, int world);
 void launch_snp_stats(const uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_t n_sid, int count_a1,
-                      int std_kind, double a, double b, int use_stats, int dtype, void* stats, void* lut,
-                      hipStream_t st);
+                      const StdArgs& sa, int dtype, void* stats, void* lut, hipStream_t st);
 void launch_decode(const uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_t n_sid, const void* lut,
                    int dtype, int order_c, void* out, uint64_t ld, hipStream_t st);
 void launch_decode_std_fused(const uint8_t* packed, uint64_t pitch, uint64_t n, uint64_t m, int count_a1,
-                             int std_kind, double a, double b, int use_stats, void* stats, void* lut, void* out,
-                             uint64_t ld, hipStream_t st);
+                             const StdArgs& sa, void* stats, void* lut, void* out, uint64_t ld, hipStream_t st);
 // iid gather: plan = repack_plan_entries(n_out) u32 and win = repack_win_entries(n_out) u32 of
 // scratch, built once per index list (launch_repack_plan, which may synchronise the stream once)
 struct RepackPlan {
@@ -209,7 +229,7 @@ void launch_repack(const uint8_t* src, uint64_t src_pitch, uint64_t n_src, const
 void launch_dense_codes(const float* Z, uint64_t ldz, uint64_t n, uint64_t m, uint8_t* packed, uint64_t pitch,
                         float* lut, unsigned int* flag, hipStream_t st);
 void launch_dense_standardize(void* val, uint64_t rows, uint64_t cols, uint64_t ld, int order_c, int dtype,
-                              int std_kind, double a, double b, int use_stats, void* stats, hipStream_t st);
+                              const StdArgs& sa, void* stats, hipStream_t st);
 void launch_subset(const void* in, int in_dt, uint64_t rows, uint64_t cols, uint64_t k, int in_order_c,
                    const uint64_t* ri, uint64_t nr, const uint64_t* ci, uint64_t nc, int out_order_c,
                    void* out, int out_dt, hipStream_t st);
@@ -368,6 +388,11 @@ void launch_tile_reduce(const float* partial, unsigned slices, uint64_t elems, f
 struct PackedSide {
     const uint8_t* P;  // codes [m][pitch]
     uint64_t pitch, n;
+};
+// ... with their SNP count and allele convention: the packed-SNP argument block of api.hip
+struct PackedSnps : PackedSide {
+    uint64_t m;
+    int count_a1;
 };
 int crt_moduli();
 extern int g_crt_kernel;  // residue SYRK form (hook "crt"): 0 = k_syrk_i8r, 1 = warp-specialised k_syrk_i8w
