@@ -457,6 +457,57 @@ int snpmi_dev_packed_tdot(const uint8_t* packed, uint64_t pitch, uint64_t n_iid,
                           int dtype, const void* V, uint64_t ldv, uint64_t k, void* G, uint64_t ldg);
 int snpmi_dev_packed_dot(const uint8_t* packed, uint64_t pitch, uint64_t n_iid, uint64_t n_sid, const void* lut,
                          int dtype, const void* W, uint64_t ldw, uint64_t k, void* Y, uint64_t ldy, int accumulate);
+/* SNP pairs straight from the packed codes: the value of pair (a, b) at iid i is
+ *   Zp[i, (a, b)] = lut0[4 a + code0(i, a)] * lut1[4 b + code1(i, b)],
+ * ONE IEEE multiply in dtype (f32 / f64) of two table entries (the LUTs of snpmi_dev_snp_stats), so
+ * the value is defined bit for bit by the two tables.  These are the columns of the reference's
+ * Pairs reader (snpreader/pairs.py:135-152), which multiplies two standardized SnpData on the host.
+ *   snpmi_dev_pair_values:  the values of a pair list               (n_iid x n_pairs)
+ *   snpmi_dev_pair_tdot:    G = Zp^T V over all pairs of two blocks (no pair column is written)
+ * Layout: every pointer is a device pointer.  A side is packed codes [.][pitch] (4-byte aligned,
+ * pitch % 64 == 0) with its table [.][4] of dtype; the two sides may be the same buffers, and may
+ * have different pitches.
+ * Errors (SNPMI_E_ARG before any launch, the output untouched): an ld that is too small (below),
+ * pitch % 64 != 0, a pitch below ceil(n_iid / 4), another dtype.
+ * Both run on the calling thread's stream and keep no state (not even scratch).
+ * iids: genotypes of iids >= n_iid never reach an output, whatever the unused codes of a column's
+ * last byte, its pad bytes up to pitch and the tables hold.
+ * NaN: as NumPy's elementwise product -- a NaN table entry (the missing code under no
+ * standardization) gives a NaN value whatever the other factor is, zero included; in the tdot a NaN
+ * value gives NaN in every column of that pair's row, whatever V holds, and no other row.
+ * Determinism: no atomics, one fixed order per sum, the same bits on every run.
+ *
+ * pair_values: out[i, c] = lut0[4 idx0[c] + code0(i, idx0[c])] * lut1[4 idx1[c] + code1(i, idx1[c])]
+ * for c < n_pairs.  idx0 / idx1 index the SNPs of side 0 / side 1 (the caller keeps them inside its
+ * buffers); they may repeat, be equal (a square) and come in any order.  F order (order_c == 0):
+ * column c at out + c * ld elements, ld >= n_iid and ld % 16 == 0, out 16-byte aligned -- the rule
+ * of snpmi_dev_decode, for the same 16-byte stores; C order: row i at out + i * ld, ld >= n_pairs.
+ * Elements between the row count and ld are not written.  n_iid == 0 or n_pairs == 0 launches
+ * nothing.
+ *
+ * pair_tdot: side a has n_a SNPs, side b n_b.  For every a < n_a and every b with b_lo[a] <= b < n_b
+ *   G[row_off[a] + b, c] = sum_i Zp[i, (a, b)] V[i, c]        c < k
+ * row_off == NULL means a * n_b, b_lo == NULL means 0; rows of G no (a, b) maps to are not written.
+ * So a rectangle of a block pair lands in the reader's pair order, the triangular diagonal blocks
+ * (b_lo skips b <= a, or b < a with singles) included, without a scatter pass.  row_off[a] + b may be
+ * negative only for b < b_lo[a]: the caller guarantees that, and that every written row is below ldg.
+ * V (n_iid rows, ldv >= n_iid) and G are F-order tall matrices as in snpmi_dev_packed_tdot: column c
+ * at base + c * ld elements.  With row_off == NULL, ldg >= n_a * n_b (else SNPMI_E_ARG).  k is any
+ * count, served in column panels of 4 / 2 / 1 (f32) or 2 / 1 (f64).  n_a, n_b or k == 0 launch
+ * nothing; n_iid == 0 writes zeros to the rows the call owns.
+ * Summation: the pair's value is rounded in dtype first (it equals what pair_values writes) and is
+ * then multiplied into V by FMA.  Per column a lane adds its 16 iids, a wave its 64 lanes, a
+ * workgroup its 4 waves (4096 iids, in dtype); the 4096-iid chunks are then added in chunk order in
+ * f64 and rounded once -- the scheme of snpmi_dev_packed_tdot.  A pair's row depends on its two
+ * SNPs, their tables and V alone: not on the rectangle, on its neighbours or on the tile (8 x 32
+ * SNPs per workgroup) it fell into. */
+int snpmi_dev_pair_values(const uint8_t* packed0, uint64_t pitch0, const void* lut0, const uint8_t* packed1,
+                          uint64_t pitch1, const void* lut1, uint64_t n_iid, const uint32_t* idx0,
+                          const uint32_t* idx1, uint64_t n_pairs, int dtype, int order_c, void* out, uint64_t ld);
+int snpmi_dev_pair_tdot(const uint8_t* packed_a, uint64_t pitch_a, const void* lut_a, uint64_t n_a,
+                        const uint8_t* packed_b, uint64_t pitch_b, const void* lut_b, uint64_t n_b, uint64_t n_iid,
+                        const int64_t* row_off, const uint32_t* b_lo, int dtype, const void* V, uint64_t ldv,
+                        uint64_t k, void* G, uint64_t ldg);
 /* GRM tiles: K_tiles holds the upper-triangle 128x128 tiles of an n x n K
  * (snpmi_grm_tile_bytes); accumulate != 0 adds to it. */
 uint64_t snpmi_grm_tile_bytes(uint64_t n_iid, int dtype);

@@ -15,11 +15,12 @@ from pysnptools_amd import _native as N
 from pysnptools_amd.util import get_num_threads
 
 # source kinds
-BED, PIECES, SNPGEN, SNPGEN_IIDS, DIST, DISTGEN, BGEN, DENSE, NONE = ("bed", "pieces", "snpgen", "snpgen_iids", "dist",
-                                                                      "distgen", "bgen", "dense", None)
+BED, PIECES, SNPGEN, SNPGEN_IIDS, DIST, DISTGEN, BGEN, PAIRS, DENSE, NONE = (
+    "bed", "pieces", "snpgen", "snpgen_iids", "dist", "distgen", "bgen", "pairs", "dense", None)
 SNPGEN_CHUNK_BYTES = 1 << 30  # packed SNPs generated in HBM per add_packed
 DISTGEN_CHUNK_BYTES = 1 << 30  # distributions generated in HBM per add_dist
 BGEN_CHUNK_BYTES = 1 << 30  # inflated BGEN blocks staged, and triples decoded from them in HBM, per launch
+PAIRS_CHUNK_BYTES = 1 << 30  # pair values written in HBM per add_dense
 
 
 def order_c(val):
@@ -43,8 +44,12 @@ def source_kind(base, rows=None):
     from pysnptools_amd.snpreader.bed import Bed
     from pysnptools_amd.snpreader.snpgen import SnpGen
 
+    from pysnptools_amd.snpreader.pairs import Pairs
+
     if _bed_pieces(base) is not None:
         return PIECES
+    if isinstance(base, Pairs):
+        return PAIRS  # (an iid subset of a Pairs takes the generic block loop, through its _read)
     if isinstance(base, _Dist2Snp):
         # (an iid subset of a DistGen or Bgen is a DIST without stored values: the generic block loop)
         if bgen_range(base.distreader) is not None:
@@ -296,3 +301,94 @@ def feed_bgen(s, p, stats, chunk_bytes=None):
         val = buf if count == widest else hbm.HbmArray((p.n, count, 3), p.dtype, "F", _base=buf, _ptr=buf.ptr)
         bgen._decode_into(val, count, 0, cols[here])
         _add_with_stats(p, stats, here, lambda st: s.add_dist(val, 0, count, p.base.max_weight, p.std, st))
+
+
+def feed_pairs(s, p, stats, chunk_bytes=None):
+    """An all-iid ``Pairs`` (any pair subset): chunks of at most ``PAIRS_CHUNK_BYTES`` of pair values
+    are written in HBM from the resident packed inner SNPs (``snpmi_dev_pair_values``), standardized
+    there by the plan's standardizer (the device-side dense standardize) and added -- the N x P values
+    never exist on the host."""
+    pairs, cols = p.base, p.col_index(np.int64)
+    pairs._resident(p.dtype)  # every chunk reads the same inner SNPs: loaded once
+    is_beta, st_fn = int(p.kind == N.STD_BETA), "snpmi_standardize_" + p.sfx
+    step = max(1, (chunk_bytes or PAIRS_CHUNK_BYTES) // (max(p.n, 1) * p.dtype.itemsize))
+    for c0 in range(0, len(cols), step):
+        here = slice(c0, min(c0 + step, len(cols)))
+        val = pairs._values(None, cols[here], "F", p.dtype, to_hbm=True)
+
+        def add(st):
+            if p.kind != N.STD_NONE:
+                N.call(st_fn, N.ptr(val), val.shape[0], val.shape[1], 0, is_beta, float(p.a), float(p.b), 1,
+                       int(p.use_stats), N.ptr(st), get_num_threads(None))
+            s.add_dense(val)
+
+        _add_with_stats(p, stats, here, add)
+
+
+# ---------------------------------------------------------------------- packed SNPs in HBM
+def at(a, offset):
+    """Device address ``offset`` bytes into an HbmArray."""
+    return ctypes.c_void_p(a.ptr + int(offset))
+
+
+def packed_chunks(p, dtype, stats, chunk_bytes, multiple=1, num_threads=None):
+    """The plan's SNPs (a Bed or SnpGen source) as packed codes in HBM, chunk by chunk: (first SNP,
+    count, packed codes, pitch, value table) in SNP order.  Per chunk: the source's packed SNPs (the
+    .bed gather and upload, or the generator), the iid repack of a subset, and the stats / value table
+    of the chunk on the selected iids (``snpmi_dev_snp_stats`` with the plan's standardizer).  A chunk
+    holds at most ``chunk_bytes`` of source codes and a multiple of ``multiple`` SNPs.  ``stats``
+    ([m, 2] of dtype) is read when the plan's standardizer is trained, else filled on the way."""
+    from pysnptools_amd import hbm
+
+    dtype = np.dtype(dtype)
+    n, m = int(p.n), int(p.m)
+    base, rows = p.base, p.rows
+    n_src = int(base.iid_count)
+    pitch = int(N.lib().snpmi_packed_pitch(n))
+    pitch_src = int(N.lib().snpmi_packed_pitch(n_src))
+    col_index = p.col_index(np.uint64)
+    is_bed = p.source == BED
+    if is_bed:
+        base._run_once()
+    count_a1 = int(bool(base.count_A1)) if is_bed else 0
+    idx = None if rows is None else hbm.asarray(N.index_array(rows))
+    step = max(multiple, chunk_bytes // pitch_src // multiple * multiple)
+    dt = N.dt_code(dtype)
+    for s0 in range(0, m, step):
+        here = slice(s0, min(s0 + step, m))
+        cnt = here.stop - here.start
+        cols = np.ascontiguousarray(col_index[here])
+        if is_bed:
+            host = np.empty((cnt, pitch_src), dtype=np.uint8)
+            N.call("snpmi_bed_gather_packed", base.filename.encode(), n_src, int(base.sid_count), N.ptr(cols), cnt,
+                   pitch_src, N.ptr(host), p.threads(num_threads))
+            packed = hbm.asarray(host)
+        else:
+            packed, _ = base._packed(cols)
+        if idx is not None:
+            sub = hbm.empty((cnt, pitch), dtype=np.uint8)
+            N.call("snpmi_dev_repack", N.ptr(packed), pitch_src, n_src, N.ptr(idx), n, cnt, N.ptr(sub), pitch)
+            packed = sub
+        lut = hbm.empty((cnt, 4), dtype=dtype)
+        st = (hbm.asarray(np.ascontiguousarray(stats[here])) if p.use_stats
+              else hbm.empty((cnt, 2), dtype=dtype))
+        N.call("snpmi_dev_snp_stats", N.ptr(packed), pitch, n, cnt, count_a1, *p.std, dt, N.ptr(st), N.ptr(lut))
+        if not p.use_stats:
+            stats[here] = st.get()
+        yield s0, cnt, packed, pitch, lut
+
+
+def load_packed(p, dtype, stats, chunk_bytes, multiple=1, num_threads=None):
+    """All of ``packed_chunks`` resident in HBM: (packed codes [m][pitch], pitch, value table [m][4])."""
+    from pysnptools_amd import hbm
+
+    dtype = np.dtype(dtype)
+    n, m = int(p.n), int(p.m)
+    pitch = int(N.lib().snpmi_packed_pitch(n))
+    packed = hbm.empty((max(m, 1), pitch), dtype=np.uint8)
+    lut = hbm.empty((max(m, 1), 4), dtype=dtype)
+    for s0, cnt, pk, _, lt in packed_chunks(p, dtype, stats, chunk_bytes, multiple, num_threads):
+        N.call("snpmi_dev_memcpy_d2d", at(packed, s0 * pitch), N.ptr(pk), cnt * pitch)
+        N.call("snpmi_dev_memcpy_d2d", at(lut, s0 * 4 * dtype.itemsize), N.ptr(lt), cnt * 4 * dtype.itemsize)
+        N.call("snpmi_stream_sync")  # the chunk's buffers are released on the way round
+    return packed, pitch, lut

@@ -130,6 +130,9 @@ _SIGS = {
     "snpmi_dev_repack": [_vp, _u64, _u64, _vp, _u64, _u64, _vp, _u64],
     "snpmi_dev_packed_tdot": [_vp, _u64, _u64, _u64, _vp, _i32, _vp, _u64, _u64, _vp, _u64],
     "snpmi_dev_packed_dot": [_vp, _u64, _u64, _u64, _vp, _i32, _vp, _u64, _u64, _vp, _u64, _i32],
+    "snpmi_dev_pair_values": [_vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _i32, _i32, _vp, _u64],
+    "snpmi_dev_pair_tdot": [_vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _u64, _vp, _vp, _i32, _vp, _u64, _u64, _vp,
+                            _u64],
     "snpmi_dev_syrk_packed": [_vp, _u64, _u64, _u64, _vp, _i32, _vp, _i32],
     "snpmi_grm_rect_bytes": [_u64, _u64, _i32],
     "snpmi_rect_diag_pairs": [_vp, _u64, _vp, _u64, _vp, _u64, _u64p],

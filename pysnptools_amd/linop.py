@@ -15,6 +15,61 @@ MATVEC_CHUNK_BYTES = 1 << 30  # packed source codes streamed per chunk (resident
 _SOURCES = (G.BED, G.SNPGEN, G.SNPGEN_IIDS)
 
 
+# ---------------------------------------------------------------------- operands and results
+# The conventions of every packed-SNP product (SnpOperator, Pairs.rmatmat): NumPy or HbmArray in, the
+# same kind out, a 1-D operand a 1-D result, empty products without device work.
+def operand(a, rows, what, dtype, xp=None):
+    """(the operand as a NumPy array or HbmArray, 1-D?, result in HBM?), checked before any device
+    work."""
+    from pysnptools_amd import hbm
+    from pysnptools_amd.util import array_module
+
+    if not isinstance(a, hbm.HbmArray):
+        a = np.asarray(a)
+    if a.ndim not in (1, 2):
+        raise ValueError("%s takes a vector or a matrix, not %d dimensions" % (what, a.ndim))
+    if a.dtype != dtype:
+        raise ValueError("%s: the operator is %s, the operand %s" % (what, dtype, a.dtype))
+    if a.shape[0] != rows:
+        raise ValueError("%s: the operand has %d rows, the operator needs %d" % (what, a.shape[0], rows))
+    to_hbm = isinstance(a, hbm.HbmArray) or array_module(xp) is hbm
+    return a, a.ndim == 1, to_hbm
+
+
+def empty_product(shape, rows, a, dtype):
+    """The all-zero product of an empty sum or an empty shape (no device work), else None."""
+    k = 1 if a.ndim == 1 else a.shape[1]
+    if shape[0] and shape[1] and k:
+        return None
+    return np.zeros((rows, k), dtype=dtype, order="F")
+
+
+def as_device(a):
+    """``a`` as a 2-D F-order HbmArray (no copy when it already is one)."""
+    from pysnptools_amd import hbm
+
+    if isinstance(a, hbm.HbmArray):
+        if a.ndim == 1:
+            return hbm.HbmArray((a.shape[0], 1), a.dtype, "F", _base=a, _ptr=a.ptr)
+        return a if a.order == "F" or 1 in a.shape else a.astype(a.dtype, order="F")
+    a = a.reshape(-1, 1) if a.ndim == 1 else a
+    return hbm.asarray(np.asfortranarray(a), order="F")
+
+
+def as_result(out, one_d, to_hbm):
+    from pysnptools_amd import hbm
+
+    if isinstance(out, hbm.HbmArray) and not to_hbm:
+        out = out.get()
+    elif to_hbm and not isinstance(out, hbm.HbmArray):
+        out = hbm.asarray(out, order="F")
+    if not one_d:
+        return out
+    if isinstance(out, hbm.HbmArray):
+        return hbm.HbmArray((out.shape[0],), out.dtype, "C", _base=out, _ptr=out.ptr)
+    return out[:, 0]
+
+
 class SnpOperator(object):
     """The ``N x M`` matrix Z of ``snpreader``'s values standardized by ``standardizer``, as an operator.
 
@@ -79,52 +134,13 @@ class SnpOperator(object):
 
     # ------------------------------------------------------------------ operands and results
     def _operand(self, a, rows, what):
-        """(the operand as a NumPy array or HbmArray, 1-D?, result in HBM?), checked before any device
-        work."""
-        from pysnptools_amd import hbm
-        from pysnptools_amd.util import array_module
-
-        if not isinstance(a, hbm.HbmArray):
-            a = np.asarray(a)
-        if a.ndim not in (1, 2):
-            raise ValueError("%s takes a vector or a matrix, not %d dimensions" % (what, a.ndim))
-        if a.dtype != self.dtype:
-            raise ValueError("%s: the operator is %s, the operand %s" % (what, self.dtype, a.dtype))
-        if a.shape[0] != rows:
-            raise ValueError("%s: the operand has %d rows, the operator needs %d" % (what, a.shape[0], rows))
-        to_hbm = isinstance(a, hbm.HbmArray) or array_module(self._xp) is hbm
-        return a, a.ndim == 1, to_hbm
+        return operand(a, rows, what, self.dtype, self._xp)
 
     def _empty(self, rows, a):
-        """The all-zero product of an empty sum or an empty shape (no device work), else None."""
-        k = 1 if a.ndim == 1 else a.shape[1]
-        if self.shape[0] and self.shape[1] and k:
-            return None
-        return np.zeros((rows, k), dtype=self.dtype, order="F")
+        return empty_product(self.shape, rows, a, self.dtype)
 
-    def _device(self, a):
-        """``a`` as a 2-D F-order HbmArray (no copy when it already is one)."""
-        from pysnptools_amd import hbm
-
-        if isinstance(a, hbm.HbmArray):
-            if a.ndim == 1:
-                return hbm.HbmArray((a.shape[0], 1), a.dtype, "F", _base=a, _ptr=a.ptr)
-            return a if a.order == "F" or 1 in a.shape else a.astype(a.dtype, order="F")
-        a = a.reshape(-1, 1) if a.ndim == 1 else a
-        return hbm.asarray(np.asfortranarray(a), order="F")
-
-    def _result(self, out, one_d, to_hbm):
-        from pysnptools_amd import hbm
-
-        if isinstance(out, hbm.HbmArray) and not to_hbm:
-            out = out.get()
-        elif to_hbm and not isinstance(out, hbm.HbmArray):
-            out = hbm.asarray(out, order="F")
-        if not one_d:
-            return out
-        if isinstance(out, hbm.HbmArray):
-            return hbm.HbmArray((out.shape[0],), out.dtype, "C", _base=out, _ptr=out.ptr)
-        return out[:, 0]
+    _device = staticmethod(as_device)
+    _result = staticmethod(as_result)
 
     # ------------------------------------------------------------------ the two kernels over the chunks
     def _tdot(self, V):
@@ -164,64 +180,16 @@ class SnpOperator(object):
         return [self._loaded]
 
     def _load(self):
-        from pysnptools_amd import hbm
-
-        n, m = self.shape
-        pitch = int(N.lib().snpmi_packed_pitch(n))
-        packed = hbm.empty((max(m, 1), pitch), dtype=np.uint8)
-        lut = hbm.empty((max(m, 1), 4), dtype=self.dtype)
-        for s0, cnt, pk, _, lt in self._stream():
-            N.call("snpmi_dev_memcpy_d2d", _at(packed, s0 * pitch), N.ptr(pk), cnt * pitch)
-            N.call("snpmi_dev_memcpy_d2d", _at(lut, s0 * 4 * self.dtype.itemsize), N.ptr(lt),
-                   cnt * 4 * self.dtype.itemsize)
-            N.call("snpmi_stream_sync")  # the chunk's buffers are released on the way round
-        return 0, m, packed, pitch, lut
+        packed, pitch, lut = G.load_packed(self._p, self.dtype, self._stats, MATVEC_CHUNK_BYTES, SEGMENT,
+                                           self._num_threads)
+        self._have_stats = True
+        return 0, self.shape[1], packed, pitch, lut
 
     def _stream(self):
-        """Chunk by chunk: the source's packed SNPs (the .bed gather and upload, or the generator),
-        the iid repack of a subset, and the stats / value table of the chunk on the selected iids."""
-        from pysnptools_amd import hbm
-
-        p, (n, m) = self._p, self.shape
-        base, rows = p.base, p.rows
-        n_src = int(base.iid_count)
-        pitch = int(N.lib().snpmi_packed_pitch(n))
-        pitch_src = int(N.lib().snpmi_packed_pitch(n_src))
-        col_index = p.col_index(np.uint64)
-        is_bed = p.source == G.BED
-        if is_bed:
-            base._run_once()
-        count_a1 = int(bool(base.count_A1)) if is_bed else 0
-        idx = None if rows is None else hbm.asarray(N.index_array(rows))
-        step = max(SEGMENT, MATVEC_CHUNK_BYTES // pitch_src // SEGMENT * SEGMENT)
-        dt = N.dt_code(self.dtype)
-        for s0 in range(0, m, step):
-            here = slice(s0, min(s0 + step, m))
-            cnt = here.stop - here.start
-            cols = np.ascontiguousarray(col_index[here])
-            if is_bed:
-                host = np.empty((cnt, pitch_src), dtype=np.uint8)
-                N.call("snpmi_bed_gather_packed", base.filename.encode(), n_src, int(base.sid_count), N.ptr(cols), cnt,
-                       pitch_src, N.ptr(host), p.threads(self._num_threads))
-                packed = hbm.asarray(host)
-            else:
-                packed, _ = base._packed(cols)
-            if idx is not None:
-                sub = hbm.empty((cnt, pitch), dtype=np.uint8)
-                N.call("snpmi_dev_repack", N.ptr(packed), pitch_src, n_src, N.ptr(idx), n, cnt, N.ptr(sub), pitch)
-                packed = sub
-            lut = hbm.empty((cnt, 4), dtype=self.dtype)
-            st = (hbm.asarray(np.ascontiguousarray(self._stats[here])) if p.use_stats
-                  else hbm.empty((cnt, 2), dtype=self.dtype))
-            N.call("snpmi_dev_snp_stats", N.ptr(packed), pitch, n, cnt, count_a1, *p.std, dt, N.ptr(st), N.ptr(lut))
-            if not p.use_stats:
-                self._stats[here] = st.get()
-            yield s0, cnt, packed, pitch, lut
+        """Chunk by chunk, by the loader every packed-SNP consumer shares (``_grm.packed_chunks``)."""
+        for chunk in G.packed_chunks(self._p, self.dtype, self._stats, MATVEC_CHUNK_BYTES, SEGMENT, self._num_threads):
+            yield chunk
         self._have_stats = True
 
 
-def _at(a, offset):
-    """Device address ``offset`` bytes into an HbmArray."""
-    import ctypes
-
-    return ctypes.c_void_p(a.ptr + int(offset))
+_at = G.at

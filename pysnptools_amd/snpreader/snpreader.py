@@ -13,6 +13,8 @@
   standardizes it there, inside one GRM session (``snpmi_grm_begin / add_dist / end``);
 * ``DistGen(...).as_snp()`` (all iids, any SNP subset) generates the distributions chunk by chunk in
   HBM (``snpmi_dev_distgen_*``) and adds each chunk to the same kind of session;
+* a ``Pairs`` (all iids, any pair subset) writes chunks of pair values in HBM from the packed inner
+  SNPs (``snpmi_dev_pair_values``), standardizes each there and adds it to one GRM session;
 * anything else (custom readers or standardizers) follows the reference's block loop,
   each block's Z Z^T still computed on the GPU.
 
@@ -224,6 +226,8 @@ def _read_bed_into_hbm(reader, order, dtype, num_threads):
     source = G.source_kind(base, rows)
     if source in (G.SNPGEN, G.SNPGEN_IIDS):
         return _snpgen_into_hbm(base, rows, cols, order, dtype)
+    if source == G.PAIRS:
+        return base._values(rows, cols, order, dtype, to_hbm=True, num_threads=num_threads)
     if source != G.BED:
         return None
     base._run_once()
@@ -326,9 +330,11 @@ def _native_grm(reader, standardizer, dtype, num_threads, diag_k_to_n, block_siz
     p = G.plan(reader, standardizer, dtype)
     if p is None or p.source in (G.NONE, G.SNPGEN_IIDS) or (p.source == G.DIST and p.src is None):
         return None
+    if p.source == G.PAIRS and p.rows is not None:
+        return None  # an iid subset of a Pairs: the generic block loop, through its _read
     group = dist_mod.current()
     multi = group is not None and group.world > 1
-    if multi and p.source in (G.SNPGEN, G.DIST, G.DISTGEN, G.BGEN):
+    if multi and p.source in (G.SNPGEN, G.DIST, G.DISTGEN, G.BGEN, G.PAIRS):
         return None  # multi-rank groups take the generic block loop
     # K stays in HBM when the source values do or ARRAY_MODULE=hbm (snpreader.py:638-643)
     src_val = p.src[0] if p.source == G.DIST else getattr(p.base, "val", None)
@@ -376,6 +382,8 @@ def _native_grm(reader, standardizer, dtype, num_threads, diag_k_to_n, block_siz
                 G.feed_distgen(s, p, stats)
             elif p.source == G.BGEN:
                 G.feed_bgen(s, p, stats)
+            elif p.source == G.PAIRS:
+                G.feed_pairs(s, p, stats)
             else:
                 G.feed_dist(s, p, stats, block_size)
     return K, p.trained(stats), float(factor[0])
