@@ -399,6 +399,33 @@ int snpmi_dev_bgen_decode_f32(const uint8_t* blocks, uint64_t blocks_bytes, cons
 int snpmi_dev_bgen_decode_f64(const uint8_t* blocks, uint64_t blocks_bytes, const uint64_t* col_table, uint64_t cols,
                               const uint64_t* iid_idx, uint64_t rows, double* out, uint64_t cols_total, uint64_t col0,
                               int out_order_c);
+/* zlib streams inflated in device memory, one wave per stream (csrc/inflate.hip; the decoder is
+ * csrc/inflate_core.hpp, no compression library is linked).  src, dst: device; table: host,
+ * [streams][4] = byte offset of the stream in src (any alignment), its stored length, byte offset
+ * of its output in dst (a multiple of 8; dst itself 8-byte aligned) and the length D it must
+ * inflate to.  Before any launch every range is checked to lie inside its buffer (SNPMI_E_INDEX)
+ * and the dst ranges to be aligned and disjoint (SNPMI_E_ARG).  status: a HOST array of `streams`
+ * words, filled before the call returns: 0, or why stream s was refused -- 1 bad zlib header,
+ * 2 input exhausted, 3 reserved block type, 4 stored LEN / NLEN mismatch, 5 bad code-length set,
+ * 6 invalid length or distance symbol, 7 distance beyond the bytes produced so far, 8 output would
+ * exceed D, 9 stream ended with fewer than D bytes, 10 Adler-32 mismatch.  A refused stream never
+ * reads outside its stored range nor writes outside its D bytes (whose content is then undefined),
+ * and does not disturb the others.  Bytes behind the Adler-32 trailer are ignored, as
+ * zlib.decompress ignores them.  streams == 0 launches nothing.  Synchronous. */
+int snpmi_dev_inflate(const uint8_t* src, uint64_t src_bytes, uint8_t* dst, uint64_t dst_bytes, const uint64_t* table,
+                      uint64_t streams, uint32_t* status);
+/* What the host checks of an inflated layout-2 genotype block, read in device memory.  blocks:
+ * device, 8-byte aligned; table: host, [blocks_n][2] = byte offset (a multiple of 8) and length of
+ * each block, inside blocks_bytes (SNPMI_E_INDEX).  rec: HOST, [blocks_n][10] = 0, or 1 when the
+ * block is shorter than 10 + n_samples bytes (then only N, K and the header ploidies are read, if
+ * it has 8 bytes); the bit depth byte; the block's N; K; the header's min and max ploidy; min and
+ * max of the low six bits of the n_samples ploidy bytes (255 and 0 when n_samples is 0); the phased
+ * byte; 10 + n_samples + ceil(2 * bits * n_samples / 8).  Synchronous. */
+int snpmi_dev_bgen_check(const uint8_t* blocks, uint64_t blocks_bytes, const uint64_t* table, uint64_t blocks_n,
+                         uint64_t n_samples, uint64_t* rec);
+/* snpmi_dev_inflate's decoder on one stream in host memory: no device is touched.  *status as
+ * above; dst[0, D) is written only.  For tests, fuzzing and sanitizer runs without a GPU. */
+int snpmi_inflate_host(const uint8_t* src, uint64_t stored, uint8_t* dst, uint64_t D, uint32_t* status);
 /* selected .bed columns (all iids) into a host buffer at `pitch` bytes per column (zero pad) --
  * the gather half of the file readers (bed.py:337-343), for the cfg5 plan's per-rank shares */
 int snpmi_bed_gather_packed(const char* path, uint64_t n_iid, uint64_t n_sid, const uint64_t* sid_idx, uint64_t n_sel,

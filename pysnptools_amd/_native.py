@@ -122,6 +122,9 @@ _SIGS = {
     "snpmi_bgen_index": [_cp, _u64, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64],
     "snpmi_dev_bgen_decode_f32": [_vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _u64, _i32],
     "snpmi_dev_bgen_decode_f64": [_vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _u64, _i32],
+    "snpmi_dev_inflate": [_vp, _u64, _vp, _u64, _vp, _u64, _vp],
+    "snpmi_dev_bgen_check": [_vp, _u64, _vp, _u64, _u64, _vp],
+    "snpmi_inflate_host": [_vp, _u64, _vp, _u64, _vp],
     "snpmi_bed_gather_packed": [_cp, _u64, _u64, _vp, _u64, _u64, _vp, _i32],
     "snpmi_dev_snp_stats": [_vp, _u64, _u64, _u64, _i32, _i32, _f64, _f64, _i32, _i32, _vp, _vp],
     "snpmi_dev_decode": [_vp, _u64, _u64, _u64, _vp, _i32, _i32, _vp, _u64],

@@ -5,7 +5,9 @@ walked by ``snpmi_bgen_open`` / ``snpmi_bgen_index`` (csrc/bgen.hip, host side),
 are inflated by Python's ``zlib`` on a thread pool, checked, packed into one page-locked buffer and
 uploaded, and ``snpmi_dev_bgen_decode_*`` unpacks the B-bit integers into the iid x sid x 3 array in
 HBM, in the requested dtype and order; ``as_snp()`` and its GRM read the triples there.  Nothing is
-written next to the input: there is no metadata cache file.
+written next to the input: there is no metadata cache file.  With ``inflate='device'`` the stored
+bytes are uploaded as they are and ``snpmi_dev_inflate`` / ``snpmi_dev_bgen_check`` inflate and check
+them in HBM; the host then only reads the file and the small check records.
 
 Supported: layout 2, compression none or zlib, every variant read biallelic, unphased and diploid,
 1 ... 32 bits.  Anything else raises ``ValueError`` naming what and where; every variant of a read
@@ -90,6 +92,15 @@ def default_id_rsid_function(sid):
     return sid, "0"
 
 
+# the status words of snpmi_dev_inflate (csrc/inflate_core.hpp), as the reason of "does not inflate"
+INFLATE_STATUS = {1: "bad zlib header", 2: "the stream is truncated", 3: "reserved block type",
+                  4: "stored block length check failed", 5: "bad code-length set",
+                  6: "invalid length or distance symbol", 7: "distance beyond the start of the output",
+                  8: "more bytes than the header's length", 9: "fewer bytes than the header's length",
+                  10: "Adler-32 mismatch"}
+INFLATE_STATUS_OVERFLOW, INFLATE_STATUS_SHORT = 8, 9
+
+
 def _round8(x):
     return (x + 7) // 8 * 8
 
@@ -137,6 +148,9 @@ class Bgen(DistReader):
     :param sample: optional GEN ``.sample`` file; overrides the samples in the \\*.bgen file
     :param num_threads: threads that inflate the genotype blocks (default: ``get_num_threads``)
     :param fresh_properties: accepted; iid, sid and pos are always fresh arrays
+    :param inflate: where the zlib genotype blocks are inflated: 'host' (default: Python's ``zlib`` on
+        the thread pool) or 'device' (the stored bytes are uploaded and inflated in HBM,
+        ``snpmi_dev_inflate``, and checked there); the values read are the same
 
     >>> from pysnptools_amd.distreader import Bgen
     >>> data_on_disk = Bgen("tests/golden/data/example.bgen")
@@ -145,8 +159,12 @@ class Bgen(DistReader):
     """
 
     def __init__(self, filename, iid_function=default_iid_function, sid_function=default_sid_function, sample=None,
-                 num_threads=None, fresh_properties=True):
+                 num_threads=None, fresh_properties=True, inflate="host"):
         super(Bgen, self).__init__()
+        if not isinstance(inflate, str) or inflate not in ("host", "device"):
+            raise ValueError("inflate must be 'host' or 'device', not {0!r}".format(inflate))
+        self._inflate_on = inflate
+        self._inflated = None  # inflate='device': the HBM buffer the blocks are inflated into (grow-only)
         self._ran_once = False
         self.filename = filename
         self._iid_function = iid_function
@@ -196,6 +214,7 @@ class Bgen(DistReader):
                 if self._staging is not None:
                     self._staging.release()
                     self._staging = None
+                self._inflated = None
 
     # ------------------------------------------------------------------ the index
     def _run_once(self):
@@ -295,28 +314,38 @@ class Bgen(DistReader):
             raise ValueError("the genotype block of {0} inflates to {1} bytes, its header says {2}"
                              .format(where, len(data), inflated))
         if len(data) < 10 + n:
-            raise ValueError("the genotype block of {0} holds {1} bytes, too few for {2} samples"
-                             .format(where, len(data), n))
+            self._check_block(where, len(data), None)
         n_here, k, pmin, pmax = struct.unpack_from("<IHBB", data, 0)
+        ploidy = np.frombuffer(data, dtype=np.uint8, count=n, offset=8) & 0x3F
+        bits = data[9 + n]
+        self._check_block(where, len(data), (n_here, k, pmin, pmax, int(ploidy.min()) if n else pmin,
+                                             int(ploidy.max()) if n else pmax, data[8 + n], bits))
+        return data, bits
+
+    def _check_block(self, where, length, fields):
+        """Refuse an inflated block of ``length`` bytes that this reader cannot decode.  ``fields``:
+        its N, K, header ploidy min and max, the samples' ploidy min and max, the phased byte and the
+        bit depth, or None when it is too short to hold them."""
+        n = self._n
+        if fields is None:
+            raise ValueError("the genotype block of {0} holds {1} bytes, too few for {2} samples"
+                             .format(where, length, n))
+        n_here, k, pmin, pmax, lo, hi, phased, bits = fields
         if n_here != n:
             raise ValueError("{0} holds {1} samples, the header {2}".format(where, n_here, n))
         if k != 2:
             raise ValueError("{0} has {1} alleles; only biallelic variants are supported".format(where, k))
-        ploidy = np.frombuffer(data, dtype=np.uint8, count=n, offset=8) & 0x3F
-        if pmin != 2 or pmax != 2 or np.any(ploidy != 2):
+        if pmin != 2 or pmax != 2 or lo != 2 or hi != 2:
             raise ValueError("{0} is not diploid throughout (ploidy {1} ... {2}); only ploidy 2 is supported"
-                             .format(where, min(pmin, int(ploidy.min()) if n else pmin),
-                                     max(pmax, int(ploidy.max()) if n else pmax)))
-        phased, bits = data[8 + n], data[9 + n]
+                             .format(where, min(pmin, lo), max(pmax, hi)))
         if phased != 0:
             raise ValueError("{0} is phased; only unphased data is supported".format(where))
         if not 1 <= bits <= 32:
             raise ValueError("{0} stores {1} bits per probability; 1 ... 32 are supported".format(where, bits))
         want = 10 + n + (2 * bits * n + 7) // 8
-        if len(data) != want:
+        if length != want:
             raise ValueError("the genotype block of {0} holds {1} bytes, {2} samples at {3} bits need {4}"
-                             .format(where, len(data), n, bits, want))
-        return data, bits
+                             .format(where, length, n, bits, want))
 
     def _chunks(self, sid_index, rows, itemsize, chunk_bytes):
         """Slices of ``sid_index`` whose blocks (each counted once per column) and whose triples both
@@ -349,29 +378,108 @@ class Bgen(DistReader):
         total = int(offsets[-1]) + 16  # the kernel's two-word windows end inside the spare bytes
         if self._staging is None:
             self._staging = _Staging()
+        threads = min(get_num_threads(self._num_threads if num_threads is None else num_threads), 64, len(uniq))
+        if self._inflate_on == "device" and self._flags & 3:
+            blocks, bits = self._stage_inflated(uniq, offsets, total, threads)
+        else:
+            blocks, bits = self._stage_on_host(uniq, offsets, total, threads)
+        table = np.empty((len(sid_index), 3), dtype=np.uint64)
+        table[:, 0], table[:, 1], table[:, 2] = offsets[:-1][inverse], bits[inverse], self._n
+        idx = None if rows is None else N.index_array(rows)
+        N.call("snpmi_dev_bgen_decode_" + N.suffix(out.dtype), N.ptr(blocks), total, N.ptr(table),
+               len(sid_index), N.ptr(idx), n_rows, N.ptr(out), int(cols_total), int(col0),
+               1 if out.order == "C" else 0)
+        return out
+
+    @staticmethod
+    def _map(threads, fn, count):
+        if threads > 1 and count > 1:
+            with ThreadPoolExecutor(max_workers=threads) as pool:
+                return list(pool.map(fn, range(count)))
+        return [fn(k) for k in range(count)]
+
+    def _stage_on_host(self, uniq, offsets, total, threads):
+        """inflate='host': the variants ``uniq`` inflated and checked on the thread pool, packed at
+        ``offsets`` of the page-locked buffer and uploaded.  Returns (HBM buffer, bit depths)."""
         self._staging.reserve(total)
         view = self._staging.view
-        threads = min(get_num_threads(self._num_threads if num_threads is None else num_threads), 64, len(uniq))
 
         def one(k):
             data, bits = self._inflate(int(uniq[k]))
             view[offsets[k]:offsets[k] + len(data)] = np.frombuffer(data, dtype=np.uint8)
             return bits
 
-        if threads > 1 and len(uniq) > 1:
-            with ThreadPoolExecutor(max_workers=threads) as pool:
-                bits = np.fromiter(pool.map(one, range(len(uniq))), dtype=np.uint64, count=len(uniq))
-        else:
-            bits = np.fromiter((one(k) for k in range(len(uniq))), dtype=np.uint64, count=len(uniq))
+        bits = np.fromiter(self._map(threads, one, len(uniq)), dtype=np.uint64, count=len(uniq))
         view[total - 16:total] = 0
         N.call("snpmi_memcpy_h2d", N.ptr(self._staging.dev), self._staging.host, total)
-        table = np.empty((len(sid_index), 3), dtype=np.uint64)
-        table[:, 0], table[:, 1], table[:, 2] = offsets[:-1][inverse], bits[inverse], self._n
-        idx = None if rows is None else N.index_array(rows)
-        N.call("snpmi_dev_bgen_decode_" + N.suffix(out.dtype), N.ptr(self._staging.dev), total, N.ptr(table),
-               len(sid_index), N.ptr(idx), n_rows, N.ptr(out), int(cols_total), int(col0),
-               1 if out.order == "C" else 0)
-        return out
+        return self._staging.dev, bits
+
+    def _stage_inflated(self, uniq, offsets, total, threads):
+        """inflate='device': the stored bytes of the variants ``uniq`` read into the page-locked
+        buffer back to back, uploaded, inflated at ``offsets`` of a second HBM buffer (one wave per
+        block) and checked there.  Returns (that buffer, bit depths)."""
+        from pysnptools_amd import hbm
+
+        at, stored, lengths = self._rec[uniq, 0], self._rec[uniq, 1], self._rec[uniq, 2]
+        src = np.concatenate(([0], np.cumsum(stored)))
+        src_total = int(src[-1])
+        self._staging.reserve(max(src_total, 1))
+        view = self._staging.view
+
+        def one(k):
+            a, b = int(src[k]), int(src[k + 1])
+            if b > a and os.preadv(self._fd, [view[a:b]], int(at[k])) != b - a:
+                raise ValueError("BGEN file is truncated: the genotype block of {0} at offset {1}"
+                                 .format(self._where(int(uniq[k])), int(at[k])))
+
+        self._map(threads, one, len(uniq))
+        if self._inflated is None or self._inflated.nbytes < total:
+            self._inflated = None
+            self._inflated = hbm.empty((total,), dtype=np.uint8)
+        blocks = self._inflated
+        N.call("snpmi_dev_memset", ctypes.c_void_p(blocks.ptr + total - 16), 0, 16)  # the decode's spare bytes
+        if src_total:
+            N.call("snpmi_memcpy_h2d", N.ptr(self._staging.dev), self._staging.host, src_total)
+        N.call("snpmi_stream_sync")
+        table = np.empty((len(uniq), 4), dtype=np.uint64)
+        table[:, 0], table[:, 1], table[:, 2], table[:, 3] = src[:-1], stored, offsets[:-1], lengths
+        status = np.zeros(len(uniq), dtype=np.uint32)
+        N.call("snpmi_dev_inflate", N.ptr(self._staging.dev), max(src_total, 1), N.ptr(blocks), total, N.ptr(table),
+               len(uniq), N.ptr(status))
+        rec = np.zeros((len(uniq), 10), dtype=np.uint64)
+        where = np.ascontiguousarray(table[:, 2:])  # (offset, length) of each inflated block
+        N.call("snpmi_dev_bgen_check", N.ptr(blocks), total, N.ptr(where), len(uniq), self._n, N.ptr(rec))
+        bad = np.flatnonzero((status != 0) | (rec[:, 0] != 0) | (rec[:, 1] < 1) | (rec[:, 1] > 32)
+                             | (rec[:, 9] != lengths.astype(np.uint64))
+                             | np.any(rec[:, 2:9] != np.array([self._n, 2, 2, 2, 2, 2, 0], dtype=np.uint64), axis=1))
+        if len(bad):  # the first variant in file order that the host route would have refused
+            k = int(bad[0])
+            self._refuse(int(uniq[k]), int(status[k]), bytes(view[int(src[k]):int(src[k + 1])]), int(lengths[k]),
+                         [int(x) for x in rec[k]])
+        return blocks, rec[:, 1].copy()
+
+    def _where(self, v):
+        return "variant {0} ('{1}') of '{2}'".format(v, self._ids[v], self.filename)
+
+    def _refuse(self, v, status, stored, inflated, rec):
+        """Raise for variant ``v``, whose device inflate ended with ``status`` or whose check record
+        ``rec`` does not pass, in the words of ``_inflate``."""
+        where = self._where(v)
+        if status in (INFLATE_STATUS_OVERFLOW, INFLATE_STATUS_SHORT):
+            # the stream disagrees with the header's length: inflate this one block here to name its own
+            try:
+                length = len(zlib.decompress(stored))
+            except zlib.error as e:
+                raise ValueError("the genotype block of {0} does not inflate: {1}".format(where, e))
+            raise ValueError("the genotype block of {0} inflates to {1} bytes, its header says {2}"
+                             .format(where, length, inflated))
+        if status:
+            raise ValueError("the genotype block of {0} does not inflate: {1}"
+                             .format(where, INFLATE_STATUS.get(status, "status {0}".format(status))))
+        self._check_block(where, inflated, None if rec[0] else (rec[2], rec[3], rec[4], rec[5],
+                                                                 rec[6] if self._n else rec[4],
+                                                                 rec[7] if self._n else rec[5], rec[8], rec[1]))
+        raise AssertionError("the check record of {0} passes".format(where))
 
     def _generate_into(self, out, sid_index, rows=None, num_threads=None, chunk_bytes=None):
         """``_decode_into`` of all of ``out`` in chunks of bounded staging."""
